@@ -22,7 +22,12 @@ N=1: BASELINE.json configs[1] = MOT17-half heads, DLA-34, 512x512, batch 1 (one 
 synthetic frames, seeded random-init weights.  Weak scaling: every rank runs the same number
 of streams.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ``--steps`` steps and prints the contract fields
+(``ms_per_step`` = milliseconds of one timed step) with what the timed loop itself yields; ``--dump-outputs DIR`` writes
+the tracks the last timed step returned (see ``dump_outputs``).  Everything else the benchmark measures needs runs of
+its own and is done only with ``--full``: the resident-frames rate and the clock levels under load, the device-only
+frame time, ``box_calibration``, the roofline figures, the CPU baseline and, on the default workload, the sparse-heads
+line and the appended ``configs``.  ``--full`` adds
   roofline      the DCNv2 kernel (dcn_mfma_kernel): algorithmic flops (2*9*Cin*Cout*h*w per
                 layer, + the fused offset/mask conv's) and algorithmic bytes (4*(Cin*h*w
                 + 27*h*w + Cout*h*w + 9*Cin*Cout + Cout)) of the 16 DCN layers / their summed launch
@@ -41,6 +46,7 @@ Rank 0 prints ONE JSON line with the contract fields plus
                 (reported baseline only)
 """
 import argparse
+import collections
 import json
 import os
 import sys
@@ -79,12 +85,17 @@ def build_parser():
                     help='also report the rate with raw u8 1080p frames handed to step() (u8 H2D + device-side '
                          'pre-processing) under "raw_u8_1080p_fps" -- never the headline value')
     ap.add_argument('--no-extra-configs', action='store_true',
-                    help='skip the BASELINE configs 3-5 / 544x960 measurements the default invocation appends as "configs"')
+                    help='skip the BASELINE configs 3-5 / 544x960 measurements --full appends as "configs"')
     ap.add_argument('--extra-steps', type=int, default=6, help='timed steps of each appended configuration')
     ap.add_argument('--sparse-heads', action='store_true',
                     help='opt.sparse_heads: regression heads evaluated at the K decode winners only (opt-in product mode, '
                          'never the headline: the reference computes dense maps)')
     ap.add_argument('--no-box-probes', action='store_true', help='box_calibration without the latency / clock probes')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what needs runs of its own (resident frames, device time, box calibration, roofline, '
+                         'CPU baseline, sparse-heads line, appended configs); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write the tracks the last timed step returned as DIR/<name>.npy (float32 / float64)')
     return ap
 
 
@@ -272,8 +283,44 @@ def cpu_baseline(cfg, heads, sd, frames_cpu, metas, opt_kw, nframes, sweep):
                        'pure-PyTorch CPU restatement of the reference path incl. DCNv2')
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frames):
+    """``frames``: what ``det.step`` returned for each frame of the last timed step, one result per stream (a
+    fast_track.TRACK_DTYPE array; a list of result dicts on the Python host path).  Writes every field of the tracks,
+    concatenated frame by frame and stream by stream, as ``tracks_<field>.npy`` (float fields float32, integer fields
+    float64, which holds them exactly) and ``tracks_offsets.npy`` (float64 [frames * streams + 1]: the tracks of frame f,
+    stream s are rows offsets[f * streams + s] .. offsets[f * streams + s + 1]).  Above 64 MB only the trailing frames of
+    the step that fit are written."""
+    from centertrack_amd import fast_track as FT
+
+    def as_tracks(r):
+        if isinstance(r, np.ndarray):
+            return r
+        arr = FT.items_to_array(r)
+        for i, it in enumerate(r):
+            for k in ('tracking_id', 'age', 'active'):
+                arr[i][k] = it.get(k, 0)
+        return arr
+    frames = [[as_tracks(r) for r in res] for res in frames]
+    names = FT.TRACK_DTYPE.names
+    kind = {n: np.float32 if FT.TRACK_DTYPE[n].base.kind == 'f' else np.float64 for n in names}
+    row_bytes = sum(np.dtype(kind[n]).itemsize * int(np.prod(FT.TRACK_DTYPE[n].shape)) for n in names)
+    nbytes = [sum(len(a) for a in f) * row_bytes + 8 * len(f) for f in frames]
+    first = 0
+    while first < len(frames) - 1 and sum(nbytes[first:]) + 8 > DUMP_MAX_BYTES:
+        first += 1
+    flat = [a for f in frames[first:] for a in f]
+    tracks = np.concatenate(flat) if flat else np.zeros(0, FT.TRACK_DTYPE)
+    os.makedirs(out_dir, exist_ok=True)
+    for n in names:
+        np.save(os.path.join(out_dir, 'tracks_%s.npy' % n), np.ascontiguousarray(tracks[n], kind[n]))
+    np.save(os.path.join(out_dir, 'tracks_offsets.npy'), np.cumsum([0] + [len(a) for a in flat]).astype(np.float64))
+
+
 # BASELINE.json configs[2..4] at their per-GPU batch + the reference's own MOT input size (datasets/mot.py:15): measured by
-# the DEFAULT invocation after the headline and appended to its line as "configs"  -- never `value`
+# --full after the headline and appended to its line as "configs" (VERDICT r4 item 3) -- never `value`
 # BASELINE configs 3-5 at their per-GPU batch, the reference's own MOT size, and the 32-stream end points of north_star's
 # synthetic sweep (VERDICT r5 item 7: driver-witnessed instead of builder-only); (name, streams, timed steps or 0 = --extra-steps)
 EXTRA_CONFIGS = (('kitti_1280x384', 4, 0), ('coco_512', 4, 0), ('nusc_800x448', 4, 0), ('mot17_544x960', 1, 0),
@@ -329,7 +376,7 @@ def main():
         except Exception as e:
             return {'error': repr(e)}
 
-    if rank == 0 and world == 1 and default_workload and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and default_workload and not args.no_extra_configs:
         out['sparse_heads'] = dict(sparse_line('mot17_512', 1), note=(
             'opt.sparse_heads (opt-in, not the reference\'s computation graph: its regression heads are dense maps that '
             'generic_decode reads at K pixels): the same workload with those heads evaluated at the K winners only; rows '
@@ -448,9 +495,24 @@ def measure(args, env, headline=True):
         torch.cuda.synchronize()
         return parallel.max_over_ranks(time.perf_counter() - t0), nfr, ndet
 
+    recorded = None
+    if headline and args.dump_outputs:
+        # keeps what step() returned for the last fps_step frames: after the timed loop, those of its last step
+        recorded = collections.deque(maxlen=fps_step)
+        step = det.step
+
+        def recording_step(*a, **kw):
+            res = step(*a, **kw)
+            recorded.append(res)
+            return res
+        det.step = recording_step
     host_frame = lambda t: pinned[t % T]
     parallel.run_steps(det, host_frame, metas, args.warmup, fps_step)
     dt, nfr, ndet = timed(host_frame, args.steps, args.warmup * fps_step)
+    if recorded is not None:
+        del det.step
+        if rank == 0:
+            dump_outputs(args.dump_outputs, list(recorded))
     fps = total_streams * nfr / dt
     rccl_ranks = 1
     gathered = None
@@ -487,7 +549,7 @@ def measure(args, env, headline=True):
     if gathered is not None:
         out['gathered'] = gathered
     clocks = None
-    if not args.no_resident:
+    if args.full and not args.no_resident:
         frames = [f.to(device) for f in frames_cpu]
         dt2, nfr2, _ = timed(lambda t: frames[t % T], args.steps)
         out['resident_frames_fps'] = round(total_streams * nfr2 / dt2, 2)
@@ -511,46 +573,47 @@ def measure(args, env, headline=True):
                     clocks = {'error': repr(e)}
     if rank == 0:
         ctx = det._ctx
-        # device-only time of one frame (graph replay or eager launches), HIP events on the launch stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 30
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(reps):
-            if ctx['graph'] is not None:
-                ctx['graph'].replay()
-            else:
-                ctx['device_frame']()
-        e1.record()
-        torch.cuda.synchronize()
-        graph_ms = e0.elapsed_time(e1) / reps
-        pre_ms = 0.0
-        if ctx.get('partial') is not None:
-            # split stem: the tracker-independent part of a frame (x / pre_img stem terms, mirrored half) is launched
-            # behind the PREVIOUS frame's graph and runs while the host associates that frame -- device work of the
-            # frame all the same, timed here on its own
+        if args.full:
+            # device-only time of one frame (graph replay or eager launches), HIP events on the launch stream
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            reps = 30
+            torch.cuda.synchronize()
             e0.record()
             for _ in range(reps):
-                ctx['pre_stage'](0)
+                if ctx['graph'] is not None:
+                    ctx['graph'].replay()
+                else:
+                    ctx['device_frame']()
             e1.record()
             torch.cuda.synchronize()
-            pre_ms = e0.elapsed_time(e1) / reps
-        dev_ms = graph_ms + pre_ms
-        out['device_ms_per_frame_batch'] = round(dev_ms, 4)
-        out['device_ms_frame_graph'] = round(graph_ms, 4)
-        out['device_ms_prestage'] = round(pre_ms, 4)
-        # wall - graph: what the host adds between two frame graphs (association, launch); the pre-stage runs inside it
-        out['host_gap_ms_per_frame_batch'] = round(1000.0 * dt / max(1, nfr) - graph_ms, 4)
-        if headline:
-            try:
-                from tools import box_calib
-                out['box_calibration'] = box_calib.box_calibration(device, probes=not args.no_box_probes)
-                if clocks is not None:
-                    out['box_calibration']['clocks_under_load'] = clocks
-            except Exception as e:
-                out['box_calibration'] = {'error': repr(e)}
+            graph_ms = e0.elapsed_time(e1) / reps
+            pre_ms = 0.0
+            if ctx.get('partial') is not None:
+                # split stem: the tracker-independent part of a frame (x / pre_img stem terms, mirrored half) is launched
+                # behind the PREVIOUS frame's graph and runs while the host associates that frame -- device work of the
+                # frame all the same, timed here on its own
+                e0.record()
+                for _ in range(reps):
+                    ctx['pre_stage'](0)
+                e1.record()
+                torch.cuda.synchronize()
+                pre_ms = e0.elapsed_time(e1) / reps
+            dev_ms = graph_ms + pre_ms
+            out['device_ms_per_frame_batch'] = round(dev_ms, 4)
+            out['device_ms_frame_graph'] = round(graph_ms, 4)
+            out['device_ms_prestage'] = round(pre_ms, 4)
+            # wall - graph: what the host adds between two frame graphs (association, launch); the pre-stage runs inside it
+            out['host_gap_ms_per_frame_batch'] = round(1000.0 * dt / max(1, nfr) - graph_ms, 4)
+            if headline:
+                try:
+                    from tools import box_calib
+                    out['box_calibration'] = box_calib.box_calibration(device, probes=not args.no_box_probes)
+                    if clocks is not None:
+                        out['box_calibration']['clocks_under_load'] = clocks
+                except Exception as e:
+                    out['box_calibration'] = {'error': repr(e)}
         out['launches_per_frame'] = len(ctx['plan']['launches'])
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             st = kernel_pass(det.model, ctx['plan'])
             d = st['dcn']
             tf = d['flops'] / (d['ms'] * 1e-3) / 1e12
@@ -622,7 +685,7 @@ def measure(args, env, headline=True):
                 fn(i)
             torch.cuda.synchronize()
             out['raw_u8_1080p_fps'] = round(B * n / (time.perf_counter() - t1), 2)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline(cfg, heads, sd, [f[0:1] for f in frames_cpu], metas, opt_kw,
                                                    args.cpu_frames, [int(t) for t in args.cpu_threads.split(',')])

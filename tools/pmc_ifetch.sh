@@ -6,14 +6,14 @@
 # states (the code does not change), SQ_IFETCH_LEVEL / SQ_IFETCH ~1.5x higher in the slow one, most for stem / decode stage 2.
 # Counters only with --kernel-trace, each group in its own pass (gpurun refuses --pmc beside the other trace domains).
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; TAG=${1:-x}; mkdir -p gpurun_out/r05_ifetch; O=$R/gpurun_out/r05_ifetch
-python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench.json 2>$O/${TAG}_bench.err
+python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench.json 2>$O/${TAG}_bench.err
 STATE=$(python -c "
 import json
 j=json.loads([l for l in open('$O/${TAG}_bench.json') if l.startswith('{')][-1])
 print('slow' if j['device_ms_per_frame_batch'] > 1.03 else 'fast', j['device_ms_per_frame_batch'], j['box_calibration']['launch_us'])")
 echo "$TAG $STATE"
 S=$(echo $STATE | cut -d' ' -f1)
-BENCH2="python $R/bench.py --steps 1 --warmup 1 --frames-per-step 8 --no-cpu-baseline --no-roofline --no-resident --no-extra-configs --no-box-probes"
+BENCH2="python $R/bench.py --full --steps 1 --warmup 1 --frames-per-step 8 --no-cpu-baseline --no-roofline --no-resident --no-extra-configs --no-box-probes"
 cd /tmp && export TMPDIR=/tmp
 for pass in "A SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVES" "B SQC_ICACHE_REQ SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "C SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES"; do
   set -- $pass; P=$1; shift
