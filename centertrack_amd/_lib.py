@@ -61,6 +61,22 @@ class DcnDesc(ctypes.Structure):
                 ('w_off_winograd', ctypes.c_void_p)]
 
 
+CT_DCN_BWD_INPUT, CT_DCN_BWD_OFFSET_MASK, CT_DCN_BWD_WEIGHT = 1, 2, 4
+
+
+class DcnBwdDesc(ctypes.Structure):
+    _fields_ = [('x', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('Cin', ctypes.c_int), ('ldx', ctypes.c_int),
+                ('om', ctypes.c_void_p), ('ldom', ctypes.c_int),
+                ('gy', ctypes.c_void_p), ('Cout', ctypes.c_int), ('ldgy', ctypes.c_int),
+                ('wT_packed', ctypes.c_void_p),
+                ('gx', ctypes.c_void_p), ('ldgx', ctypes.c_int),
+                ('gom', ctypes.c_void_p), ('ldgom', ctypes.c_int),
+                ('gw', ctypes.c_void_p), ('gb', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+                ('flags', ctypes.c_int)]
+
+
 CT_MAX_FUSED_HEADS = 8
 
 
@@ -165,7 +181,8 @@ ABI_VERSION = 103       # CT_ABI_VERSION of include/centertrack_hip.h
 
 EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_elems', 'ct_pack_conv_weight',
            'ct_packed_winograd_elems', 'ct_pack_winograd_weight', 'ct_conv2d',
-           'ct_conv2d_workspace_bytes', 'ct_heads_fused', 'ct_dcn_v2', 'ct_dcn_v2_workspace_bytes', 'ct_dcn_v2_offsets_bytes', 'ct_dcn_v2_group', 'ct_dcn_v2_group_workspace_bytes', 'ct_dcn_v2_group_plan', 'ct_stem_forward',
+           'ct_conv2d_workspace_bytes', 'ct_heads_fused', 'ct_dcn_v2', 'ct_dcn_v2_workspace_bytes', 'ct_dcn_v2_offsets_bytes', 'ct_dcn_v2_group', 'ct_dcn_v2_group_workspace_bytes', 'ct_dcn_v2_group_plan',
+           'ct_dcn_v2_backward', 'ct_dcn_v2_backward_workspace_bytes', 'ct_packed_dcn_weight_t_elems', 'ct_pack_dcn_weight_t', 'ct_stem_forward',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
            'ct_decode_pose', 'ct_render_pre_hm',
@@ -225,6 +242,12 @@ def load():
     lib.ct_dcn_v2_group_workspace_bytes.restype = sz
     lib.ct_dcn_v2_group_workspace_bytes.argtypes = [ctypes.POINTER(DcnDesc)]
     lib.ct_dcn_v2_group_plan.argtypes = [ctypes.POINTER(DcnDesc), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
+    lib.ct_dcn_v2_backward.argtypes = [ctypes.POINTER(DcnBwdDesc), p]
+    lib.ct_dcn_v2_backward_workspace_bytes.restype = sz
+    lib.ct_dcn_v2_backward_workspace_bytes.argtypes = [ctypes.POINTER(DcnBwdDesc)]
+    lib.ct_packed_dcn_weight_t_elems.restype = sz
+    lib.ct_packed_dcn_weight_t_elems.argtypes = [i, i]
+    lib.ct_pack_dcn_weight_t.argtypes = [p, p, i, i, p]
     lib.ct_stem_forward.argtypes = [p, p, p, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_stem_forward_parts.argtypes = [p, p, p, p, i, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_maxpool2x2.argtypes = [p, i, i, i, i, i, p, i, p]

@@ -11,10 +11,17 @@ conv_offset_mask.bias``), backed by ``ct_conv2d`` (offset/mask conv, sigmoid fus
 Placing / aliasing this file as ``model/networks/DCNv2/dcn_v2.py`` makes the reference's
 ``dla.py`` run on the HIP kernel unchanged.
 
-Inference only (the reference trains through upstream's backward; out of scope), CUDA
-tensors only: there is no CPU fallback.  Supported geometry is what the hot path uses:
+CUDA tensors only: there is no CPU fallback.  Supported geometry is what the hot path uses:
 3x3, stride 1, padding 1, dilation 1, one deformable group, Cin a multiple of 32.
+
+Training is opt-in: by default the three ``forward``s run under ``no_grad`` exactly as an
+inference build does.  After ``set_trainable(True)`` (or inside ``with trainable():``) and with
+autograd enabled they return tensors with a ``grad_fn`` whose backward is ``ct_dcn_v2_backward``
+(gradients for input, offset, mask, weight and bias).  The input gradient is
+accumulated with float atomics and is equal from run to run only to fp32 rounding; the other
+four are bitwise reproducible.
 """
+import contextlib
 import math
 
 import torch
@@ -54,11 +61,79 @@ def _om_view(offset, mask):
     return ops.View(om.buf, 0, 27)
 
 
+_trainable = False
+
+
+def set_trainable(flag):
+    """Switch the differentiable path of ``dcn_v2_conv`` / ``DCNv2`` / ``DCN`` on or off (default: off).  Returns the
+    previous setting.  Off, every call is today's inference call whatever ``requires_grad`` or ``module.training`` say."""
+    global _trainable
+    was = _trainable
+    _trainable = bool(flag)
+    return was
+
+
+def is_trainable():
+    return _trainable
+
+
+@contextlib.contextmanager
+def trainable(flag=True):
+    was = set_trainable(flag)
+    try:
+        yield
+    finally:
+        set_trainable(was)
+
+
+def _differentiable():
+    return _trainable and torch.is_grad_enabled()
+
+
+class _DCNv2Function(torch.autograd.Function):
+    """``ct_dcn_v2`` forward (the inference kernel, unchanged) + ``ct_dcn_v2_backward``.  ``packs`` = the (forward,
+    transposed) fragment packings of ``weight`` when the caller caches them, else None."""
+
+    @staticmethod
+    def forward(ctx, input, offset, mask, weight, bias, packs):
+        x = ops.view_from_nchw(input)
+        om = _om_view(offset.float(), mask.float())
+        wp, wT = packs if packs is not None else (ops.pack_weight(weight.detach()), None)
+        out = ops.dcn_v2(x, om, wp, weight.shape[0], shift=None if bias is None else bias.detach().contiguous())
+        ctx.x, ctx.om, ctx.wT = x, om, wT
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(weight)
+        return ops.view_to_nchw(out)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        weight, = ctx.saved_tensors
+        need_x, need_off, need_mask, need_w, need_b = ctx.needs_input_grad[:5]
+        need_om = need_off or need_mask
+        wT = ctx.wT
+        if (need_x or need_om) and wT is None:
+            wT = ops.pack_weight_t(weight.detach())
+        gy = ops.view_from_nchw(grad_out)
+        gx, gom, gw, gb = ops.dcn_v2_backward(ctx.x, ctx.om, gy, wT, need_x=need_x, need_om=need_om, need_w=need_w,
+                                              need_b=need_b and ctx.has_bias)
+        return (ops.view_to_nchw(gx) if need_x else None,
+                ops.view_to_nchw(gom.slice(0, 18)) if need_off else None,
+                ops.view_to_nchw(gom.slice(18, 9)) if need_mask else None,
+                gw if need_w else None, gb if need_b and ctx.has_bias else None, None)
+
+
 def dcn_v2_conv(input, offset, mask, weight, bias, stride=1, padding=1, dilation=1, deformable_groups=1):
-    """Upstream ``dcn_v2_conv = _DCNv2.apply`` (forward only).  offset [B,18,H,W] with (dy,dx)
-    interleaved per tap, mask [B,9,H,W] (already sigmoid-ed), weight [Co,Ci,3,3], bias [Co]."""
+    """Upstream ``dcn_v2_conv = _DCNv2.apply``.  offset [B,18,H,W] with (dy,dx) interleaved per tap, mask [B,9,H,W]
+    (already sigmoid-ed), weight [Co,Ci,3,3], bias [Co].  Differentiable under ``trainable()``."""
     _need_cuda(input)
     _check_geometry(tuple(weight.shape[2:]), stride, padding, dilation, deformable_groups, input.shape[1])
+    if _differentiable():
+        return _DCNv2Function.apply(input, offset, mask, weight, bias, None)
+    return _dcn_v2_conv_inference(input, offset, mask, weight, bias)
+
+
+@torch.no_grad()
+def _dcn_v2_conv_inference(input, offset, mask, weight, bias):
     x = ops.view_from_nchw(input)
     om = _om_view(offset.float(), mask.float())
     wp = ops.pack_weight(weight.detach())
@@ -87,18 +162,26 @@ class DCNv2(nn.Module):
         self.weight.data.uniform_(-stdv, stdv)
         self.bias.data.zero_()
 
-    def _pack(self, name, t):
+    def _pack(self, name, t, pack=ops.pack_weight):
         """MFMA-fragment packing of a weight, redone only when the parameter changes."""
         key = (t.data_ptr(), t._version, t.device)
         hit = self._packed.get(name)
         if hit is None or hit[0] != key:
-            hit = (key, ops.pack_weight(t.detach()))
+            hit = (key, pack(t.detach()))
             self._packed[name] = hit
         return hit[1]
 
-    @torch.no_grad()
+    def _packs(self):
+        return self._pack('weight', self.weight), self._pack('weight_t', self.weight, ops.pack_weight_t)
+
     def forward(self, input, offset, mask):
         _need_cuda(input)
+        if _differentiable():
+            return _DCNv2Function.apply(input, offset, mask, self.weight, self.bias, self._packs())
+        return self._forward_inference(input, offset, mask)
+
+    @torch.no_grad()
+    def _forward_inference(self, input, offset, mask):
         x = ops.view_from_nchw(input)
         om = _om_view(offset.float(), mask.float())
         out = ops.dcn_v2(x, om, self._pack('weight', self.weight), self.out_channels, shift=self.bias.detach())
@@ -120,9 +203,19 @@ class DCN(DCNv2):
         self.conv_offset_mask.weight.data.zero_()
         self.conv_offset_mask.bias.data.zero_()
 
-    @torch.no_grad()
     def forward(self, input):
         _need_cuda(input)
+        if _differentiable():
+            # as upstream: the offset/mask conv, chunk / cat / sigmoid in torch (their backward is torch's), the
+            # deformable conv through the Function
+            out = self.conv_offset_mask(input)
+            o1, o2, mask = torch.chunk(out, 3, dim=1)
+            offset = torch.cat((o1, o2), dim=1)
+            return _DCNv2Function.apply(input, offset, torch.sigmoid(mask), self.weight, self.bias, self._packs())
+        return self._forward_inference(input)
+
+    @torch.no_grad()
+    def _forward_inference(self, input):
         x = ops.view_from_nchw(input)
         B, H, W = x.N, x.H, x.W
         # ``o1, o2, mask = chunk(out, 3, 1); offset = cat(o1, o2)`` is out[:, :18]; the sigmoid of

@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import CT_OUT_NCHW, CT_RELU, ConvDesc, DcnDesc, DecodeDesc
+from ._lib import CT_OUT_NCHW, CT_RELU, ConvDesc, DcnBwdDesc, DcnDesc, DecodeDesc
 
 
 class View(object):
@@ -193,6 +193,66 @@ def dcn_v2(x, om, wp, Cout, scale=None, shift=None, relu=False, out=None, split_
             d.workspace, d.workspace_bytes = ws.data_ptr(), need
     _lib.check(lib.ct_dcn_v2(ctypes.byref(d), _lib.stream_ptr()), 'ct_dcn_v2')
     return out
+
+
+def pack_weight_t(w):
+    """OIHW 3x3 DCN weight -> the transposed fragment layout ct_dcn_v2_backward contracts gy with (centertrack_hip.h)."""
+    lib = _lib.load()
+    w = w.contiguous().float()
+    Cout, Cin, ks, ks2 = w.shape
+    assert ks == 3 and ks2 == 3 and Cin % 16 == 0
+    out = torch.empty(lib.ct_packed_dcn_weight_t_elems(Cout, Cin), dtype=torch.float32, device=w.device)
+    _lib.check(lib.ct_pack_dcn_weight_t(w.data_ptr(), out.data_ptr(), Cout, Cin, _lib.stream_ptr()), 'ct_pack_dcn_weight_t')
+    return out
+
+
+def make_dcn_bwd_desc(x, om, gy, wT=None, gx=None, gom=None, gw=None, gb=None, workspace=None):
+    """ct_dcn_bwd_desc over caller-owned buffers; the gradients to compute are the output buffers given (``gb`` rides
+    with ``gw``)."""
+    d = DcnBwdDesc()
+    d.x, d.N, d.H, d.W, d.Cin, d.ldx = x.ptr, x.N, x.H, x.W, x.C, x.ld
+    d.om, d.ldom = om.ptr, om.ld
+    d.gy, d.Cout, d.ldgy = gy.ptr, gy.C, gy.ld
+    d.wT_packed = _p(wT)
+    flags = 0
+    if gx is not None:
+        d.gx, d.ldgx = gx.ptr, gx.ld
+        flags |= _lib.CT_DCN_BWD_INPUT
+    if gom is not None:
+        d.gom, d.ldgom = gom.ptr, gom.ld
+        flags |= _lib.CT_DCN_BWD_OFFSET_MASK
+    if gw is not None:
+        d.gw, d.gb = gw.data_ptr(), _p(gb)
+        flags |= _lib.CT_DCN_BWD_WEIGHT
+    d.flags = flags
+    if workspace is not None:
+        d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return d
+
+
+def dcn_v2_backward(x, om, gy, wT=None, need_x=True, need_om=True, need_w=True, need_b=True):
+    """Gradients of ``dcn_v2(x, om, w) + bias`` for the incoming gradient ``gy`` (NHWC views; ``om`` = the forward's
+    offset/mask map, mask after the sigmoid; ``wT`` = pack_weight_t(w), needed for ``need_x`` / ``need_om``).
+    Returns ``(gx view, gom view [N,H,W,27 of 32], gw OIHW, gb)``, None for what was not asked for -- no buffer is
+    allocated and no kernel runs for those.  ``gx`` is summed with float atomics (equal from run to run only to fp32
+    rounding); the other three are bitwise reproducible."""
+    lib = _lib.load()
+    dev = x.buf.device
+    if not (need_x or need_om or need_w or need_b):
+        return None, None, None, None
+    if (need_x or need_om) and wT is None:
+        raise _lib.CTError('dcn_v2_backward: the input / offset / mask gradients need the transposed weight packing')
+    gx = new_view(x.N, x.H, x.W, x.C, dev) if need_x else None
+    gom = View(torch.empty((x.N, x.H, x.W, 32), dtype=torch.float32, device=dev), 0, 27) if need_om else None
+    gw = torch.empty((gy.C, x.C, 3, 3), dtype=torch.float32, device=dev) if need_w or need_b else None
+    gb = torch.empty(gy.C, dtype=torch.float32, device=dev) if need_b else None
+    d = make_dcn_bwd_desc(x, om, gy, wT, gx, gom, gw, gb)
+    need = lib.ct_dcn_v2_backward_workspace_bytes(ctypes.byref(d))
+    if need:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    _lib.check(lib.ct_dcn_v2_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_dcn_v2_backward')
+    return gx, gom, (gw if need_w else None), gb
 
 
 def stem(x, pre_img, pre_hm, w_x, w_img, w_hm, scale3, shift3, out=None):

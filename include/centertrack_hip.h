@@ -40,7 +40,7 @@ extern "C" {
  * 102 = ct_decode_desc.sparse (sparse heads); 103 = the ct_calib_* box probes left this header and the library (they are
  * diagnostics of the measuring box: tools/micro/probes.hip -> tools/micro/libct_probes.so; ct_dcn_desc.w_off_winograd).
  * Added under 103 without a layout change: ct_dcn_desc.algo 53264 / 532128 / 63264 / 632128 (persistent DCN launch), the
- * tuning keys "dcn_slots" and "dcn_xcd". */
+ * tuning keys "dcn_slots" and "dcn_xcd"; ct_dcn_bwd_desc and ct_dcn_v2_backward (a new descriptor and new symbols). */
 #define CT_ABI_VERSION 103
 
 const char *ct_last_error(void);
@@ -215,6 +215,41 @@ size_t ct_dcn_v2_group_workspace_bytes(const ct_dcn_desc *d);
  * output pointers may still be NULL) and returns CT_OK with *workspace_bytes (0 = the layer finishes in its MAIN
  * launch) and *splits (K splits the launch will use), or the launch's error code (see ct_last_error). */
 int ct_dcn_v2_group_plan(const ct_dcn_desc *d, size_t *workspace_bytes, int *splits);
+
+/* ---- backward of the modulated deformable convolution (training through the drop-in DCN module) --------------
+ * Replaces DCNv2's _ext.dcn_v2_backward (upstream src/cuda/dcn_v2_cuda.cu: modulated_deformable_col2im,
+ * _col2im_coord and two SGEMMs over a [9*Cin, H*W] column buffer per image) for y = ct_dcn_v2(x, om, w) + bias with no
+ * scale / ReLU, same geometry as the forward (3x3, stride 1, pad 1, dil 1, dg 1, Cin % 32 == 0), without a column
+ * buffer.  The specification is torch.autograd of oracle/dcn_v2.py::dcn_v2_conv; at an integer sample position the
+ * offset gradient is the one-sided derivative towards the next cell, as upstream's.
+ *   x, gy, gx: NHWC views [N,H,W,Cin] / [N,H,W,Cout] / [N,H,W,Cin]; om / gom: the offset/mask map of the forward and
+ *   its gradient, [N,H,W,>=27] (channels 2k, 2k+1 = d/d(dy,dx) of tap k, 18+k = d/d(mask AFTER the sigmoid); further
+ *   channels of gom are not written); gw: OIHW [Cout,Cin,3,3]; gb: [Cout] or NULL.
+ *   wT_packed: DCN.weight in the transposed fragment layout [tap][Cin/16][CoutPad/16][64 lanes][4] of
+ *   ct_pack_dcn_weight_t -- lane l, element j = w[co = 16*cb + 4*(l>>4) + j][ci = 16*c16 + (l&15)][tap] -- the B operand
+ *   of gcol = gy . W; needed for CT_DCN_BWD_INPUT / CT_DCN_BWD_OFFSET_MASK only.
+ *   flags: which gradients to compute; buffers of the others may be NULL and are not touched.  CT_DCN_BWD_WEIGHT needs a
+ *   workspace of ct_dcn_v2_backward_workspace_bytes(d) bytes (K-slab partials).  gx is zero-filled by the call and then
+ *   accumulated with float atomics: it is NOT bitwise reproducible from run to run; gom, gw and gb are.
+ *   Every view must stay below 2 GiB (N*H*W*ld*4): the kernels address a view through one buffer descriptor. */
+#define CT_DCN_BWD_INPUT 1        /* gx */
+#define CT_DCN_BWD_OFFSET_MASK 2  /* gom */
+#define CT_DCN_BWD_WEIGHT 4       /* gw (+ gb when not NULL) */
+typedef struct ct_dcn_bwd_desc {
+    const float *x; int N, H, W, Cin, ldx;
+    const float *om; int ldom;
+    const float *gy; int Cout, ldgy;
+    const float *wT_packed;
+    float *gx; int ldgx;
+    float *gom; int ldgom;
+    float *gw; float *gb;
+    float *workspace; size_t workspace_bytes;
+    int flags;
+} ct_dcn_bwd_desc;
+int ct_dcn_v2_backward(const ct_dcn_bwd_desc *d, void *stream);
+size_t ct_dcn_v2_backward_workspace_bytes(const ct_dcn_bwd_desc *d);   /* 0 without CT_DCN_BWD_WEIGHT or for a rejected descriptor */
+size_t ct_packed_dcn_weight_t_elems(int Cout, int Cin);
+int ct_pack_dcn_weight_t(const float *w_oihw, float *packed, int Cout, int Cin, void *stream);
 
 /* ---- the three 7x7 stems, fused --------------------------------------------------
  * Replaces DLA.forward's base_layer / pre_img_layer / pre_hm_layer and their sum
