@@ -77,6 +77,24 @@ class DcnBwdDesc(ctypes.Structure):
                 ('flags', ctypes.c_int)]
 
 
+CT_LOSS_FOCAL, CT_LOSS_L1, CT_LOSS_L1_DEPTH, CT_LOSS_BCE, CT_LOSS_ROT = range(5)
+CT_LOSS_MAX_HEADS = 16
+CT_LOSS_MAX_SLOTS = 8192
+
+
+class LossHead(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int), ('logits', ctypes.c_void_p), ('C', ctypes.c_int),
+                ('target', ctypes.c_void_p), ('mask', ctypes.c_void_p), ('ind', ctypes.c_void_p),
+                ('cat', ctypes.c_void_p), ('M', ctypes.c_int), ('grad', ctypes.c_void_p)]
+
+
+class LossDesc(ctypes.Structure):
+    _fields_ = [('B', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('heads', ctypes.POINTER(LossHead)), ('nheads', ctypes.c_int),
+                ('loss', ctypes.c_void_p), ('grad_loss', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
 CT_MAX_FUSED_HEADS = 8
 
 
@@ -182,7 +200,8 @@ ABI_VERSION = 103       # CT_ABI_VERSION of include/centertrack_hip.h
 EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_elems', 'ct_pack_conv_weight',
            'ct_packed_winograd_elems', 'ct_pack_winograd_weight', 'ct_conv2d',
            'ct_conv2d_workspace_bytes', 'ct_heads_fused', 'ct_dcn_v2', 'ct_dcn_v2_workspace_bytes', 'ct_dcn_v2_offsets_bytes', 'ct_dcn_v2_group', 'ct_dcn_v2_group_workspace_bytes', 'ct_dcn_v2_group_plan',
-           'ct_dcn_v2_backward', 'ct_dcn_v2_backward_workspace_bytes', 'ct_packed_dcn_weight_t_elems', 'ct_pack_dcn_weight_t', 'ct_stem_forward',
+           'ct_dcn_v2_backward', 'ct_dcn_v2_backward_workspace_bytes', 'ct_packed_dcn_weight_t_elems', 'ct_pack_dcn_weight_t',
+           'ct_generic_loss_forward', 'ct_generic_loss_backward', 'ct_generic_loss_workspace_bytes', 'ct_stem_forward',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
            'ct_decode_pose', 'ct_render_pre_hm',
@@ -248,6 +267,10 @@ def load():
     lib.ct_packed_dcn_weight_t_elems.restype = sz
     lib.ct_packed_dcn_weight_t_elems.argtypes = [i, i]
     lib.ct_pack_dcn_weight_t.argtypes = [p, p, i, i, p]
+    lib.ct_generic_loss_forward.argtypes = [ctypes.POINTER(LossDesc), p]
+    lib.ct_generic_loss_backward.argtypes = [ctypes.POINTER(LossDesc), p]
+    lib.ct_generic_loss_workspace_bytes.restype = sz
+    lib.ct_generic_loss_workspace_bytes.argtypes = [ctypes.POINTER(LossDesc)]
     lib.ct_stem_forward.argtypes = [p, p, p, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_stem_forward_parts.argtypes = [p, p, p, p, i, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_maxpool2x2.argtypes = [p, i, i, i, i, i, p, i, p]

@@ -255,6 +255,80 @@ def dcn_v2_backward(x, om, gy, wT=None, need_x=True, need_om=True, need_w=True, 
     return gx, gom, (gw if need_w else None), gb
 
 
+def make_loss_desc(heads, grads=None):
+    """``ct_loss_desc`` of ``heads`` = [(kind, logits [B,C,H,W], target, mask, ind, cat or None)], every tensor cuda,
+    contiguous, fp32 (ind / cat int64).  Returns (descriptor, keep-alive list)."""
+    if not heads:
+        raise _lib.CTError('generic_loss: no heads')
+    B, _, H, W = heads[0][1].shape
+    arr = (_lib.LossHead * len(heads))()
+    for i, (kind, x, target, mask, ind, cat) in enumerate(heads):
+        for t, dt in ((x, torch.float32), (target, torch.float32), (mask, torch.float32), (ind, torch.int64),
+                      (cat, torch.int64)):
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise _lib.CTError('generic_loss runs on an MI355X only (got a %s tensor); no CPU fallback' % t.device)
+            if t.dtype != dt or not t.is_contiguous():
+                raise _lib.CTError('generic_loss: head %d wants contiguous %s tensors (centertrack_amd.losses prepares them)'
+                                   % (i, dt))
+        if x.dim() != 4 or x.shape[0] != B or tuple(x.shape[2:]) != (H, W):
+            raise _lib.CTError('generic_loss: head %d is %s, the first head [%d, C, %d, %d]' % (i, tuple(x.shape), B, H, W))
+        C, M = x.shape[1], ind.numel() // B
+        want = {_lib.CT_LOSS_FOCAL: (x.numel(), B * M, B * M), _lib.CT_LOSS_ROT: (B * M * 2, B * M, B * M * 2)}.get(
+            kind, (B * M * C, B * M * C, 0))
+        if ind.numel() != B * M or (target.numel(), mask.numel(), 0 if cat is None else cat.numel()) != want:
+            raise _lib.CTError('generic_loss: head %d (kind %d): target / mask / ind / cat sizes do not fit B=%d M=%d C=%d'
+                               % (i, kind, B, M, C))
+        h = arr[i]
+        h.kind, h.logits, h.C, h.target, h.mask, h.ind, h.cat, h.M = (kind, x.data_ptr(), C, target.data_ptr(), mask.data_ptr(),
+                                                                    ind.data_ptr(), _p(cat), M)
+        h.grad = _p(grads[i]) if grads is not None else None
+    d = _lib.LossDesc()
+    d.B, d.H, d.W, d.heads, d.nheads = B, H, W, arr, len(heads)
+    return d, arr
+
+
+def _loss_workspace(lib, d, dev):
+    need = lib.ct_generic_loss_workspace_bytes(ctypes.byref(d))
+    if not need:
+        raise _lib.CTError('ct_generic_loss_workspace_bytes: %s' % lib.ct_last_error().decode())
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    return ws
+
+
+def generic_loss_forward(heads):
+    """The per-head losses [len(heads)] of one stack (``make_loss_desc`` for ``heads``): two launches, no host sync."""
+    lib = _lib.load()
+    d, _keep = make_loss_desc(heads)
+    dev = heads[0][1].device
+    loss = torch.empty(len(heads), dtype=torch.float32, device=dev)
+    _ws = _loss_workspace(lib, d, dev)
+    d.loss = loss.data_ptr()
+    _lib.check(lib.ct_generic_loss_forward(ctypes.byref(d), _lib.stream_ptr()), 'ct_generic_loss_forward')
+    return loss
+
+
+def generic_loss_backward(heads, grad_loss, needs=None):
+    """d(sum_i grad_loss[i] * loss[i]) / d(logits) per head of ``heads``: a list of [B,C,H,W] tensors, None where
+    ``needs[i]`` is false (no buffer is allocated for those).  Three launches, bitwise reproducible."""
+    lib = _lib.load()
+    needs = [True] * len(heads) if needs is None else list(needs)
+    if not any(needs):
+        return [None] * len(heads)
+    grads = [torch.empty_like(h[1]) if n else None for h, n in zip(heads, needs)]
+    d, _keep = make_loss_desc(heads, grads)
+    dev = heads[0][1].device
+    grad_loss = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+    if grad_loss.numel() != len(heads):
+        raise _lib.CTError('generic_loss_backward: grad_loss has %d elements for %d heads' % (grad_loss.numel(), len(heads)))
+    _ws = _loss_workspace(lib, d, dev)
+    d.grad_loss = grad_loss.data_ptr()
+    _lib.check(lib.ct_generic_loss_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_generic_loss_backward')
+    return grads
+
+
 def stem(x, pre_img, pre_hm, w_x, w_img, w_hm, scale3, shift3, out=None):
     N, _, H, W = x.shape
     if out is None:

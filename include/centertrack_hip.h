@@ -40,7 +40,8 @@ extern "C" {
  * 102 = ct_decode_desc.sparse (sparse heads); 103 = the ct_calib_* box probes left this header and the library (they are
  * diagnostics of the measuring box: tools/micro/probes.hip -> tools/micro/libct_probes.so; ct_dcn_desc.w_off_winograd).
  * Added under 103 without a layout change: ct_dcn_desc.algo 53264 / 532128 / 63264 / 632128 (persistent DCN launch), the
- * tuning keys "dcn_slots" and "dcn_xcd"; ct_dcn_bwd_desc and ct_dcn_v2_backward (a new descriptor and new symbols). */
+ * tuning keys "dcn_slots" and "dcn_xcd"; ct_dcn_bwd_desc and ct_dcn_v2_backward (a new descriptor and new symbols);
+ * ct_loss_head / ct_loss_desc and ct_generic_loss_* (the training loss: new descriptors and new symbols). */
 #define CT_ABI_VERSION 103
 
 const char *ct_last_error(void);
@@ -250,6 +251,53 @@ int ct_dcn_v2_backward(const ct_dcn_bwd_desc *d, void *stream);
 size_t ct_dcn_v2_backward_workspace_bytes(const ct_dcn_bwd_desc *d);   /* 0 without CT_DCN_BWD_WEIGHT or for a rejected descriptor */
 size_t ct_packed_dcn_weight_t_elems(int Cout, int Cin);
 int ct_pack_dcn_weight_t(const float *w_oihw, float *packed, int Cout, int Cin, void *stream);
+
+/* ---- the training loss (GenericLoss, trainer.py:20-86 + model/losses.py), forward and backward (additions under ABI
+ * 103).  Every head map is the RAW head output (logits), fp32 NCHW [B,C,H,W], contiguous; ind / cat are int64, masks and
+ * targets fp32.  One call serves all heads of a stack; the number of launches does not depend on the head count
+ * (forward 2, backward 3).  No host synchronisation, no atomics: every sum goes through per-workgroup partials that are
+ * added in a fixed order, so losses and gradients are bitwise equal from run to run.
+ *   kind                target            mask        ind     cat               loss
+ *   CT_LOSS_FOCAL       [B,C,H,W]         [B,M]       [B,M]   [B,M] class       FastFocalLoss on clamp(sigmoid(x), 1e-4, 1-1e-4)
+ *   CT_LOSS_L1          [B,M,C]           [B,M,C]     [B,M]   NULL              sum|x*mask - target*mask| / (sum(mask) + 1e-4)
+ *   CT_LOSS_L1_DEPTH    [B,M,C]           [B,M,C]     [B,M]   NULL              the same on 1 / (sigmoid(x) + 1e-6) - 1
+ *   CT_LOSS_BCE         [B,M,C]           [B,M,C]     [B,M]   NULL              sum(mask * bce_with_logits) / (sum(mask) + 1e-4)
+ *   CT_LOSS_ROT (C = 8) [B,M,2] rotres    [B,M]       [B,M]   [B,M,2] rotbin    compute_rot_loss (losses.py:161-192)
+ * A slot whose ind is outside [0, H*W) or (focal) whose cat is outside [0, C) reads and writes nothing and counts as a
+ * slot with mask 0 (for CT_LOSS_ROT: mask 0 and rotbin 0) -- the reference raises there, which needs a host sync.
+ * Backward: grad_loss[i] is the incoming gradient of loss[i] (a DEVICE pointer, e.g. weights[head] / num_stacks times
+ * d(tot)); heads[i].grad receives d/d(logits) for the WHOLE map [B,C,H,W] (zero away from the slots for the slot
+ * kinds) or is NULL to skip that head.  Slots of one image that name the same element are summed in ascending slot
+ * order by the lowest of them, which does one plain store.
+ * workspace: ct_generic_loss_workspace_bytes(d) bytes, the same for both calls (the backward does not need the forward's
+ * contents). */
+#define CT_LOSS_FOCAL 0
+#define CT_LOSS_L1 1
+#define CT_LOSS_L1_DEPTH 2
+#define CT_LOSS_BCE 3
+#define CT_LOSS_ROT 4
+#define CT_LOSS_MAX_HEADS 16
+#define CT_LOSS_MAX_SLOTS 8192    /* largest M of one head (hp_ind: max_objs * 17) */
+typedef struct ct_loss_head {
+    int kind;
+    const float *logits; int C;
+    const float *target;
+    const float *mask;
+    const long long *ind;
+    const long long *cat;
+    int M;
+    float *grad;                  /* backward only */
+} ct_loss_head;
+typedef struct ct_loss_desc {
+    int B, H, W;
+    const ct_loss_head *heads; int nheads;      /* HOST array */
+    float *loss;                  /* DEVICE [nheads], forward only */
+    const float *grad_loss;       /* DEVICE [nheads], backward only */
+    void *workspace; size_t workspace_bytes;
+} ct_loss_desc;
+int ct_generic_loss_forward(const ct_loss_desc *d, void *stream);
+int ct_generic_loss_backward(const ct_loss_desc *d, void *stream);
+size_t ct_generic_loss_workspace_bytes(const ct_loss_desc *d);   /* 0 for a rejected descriptor */
 
 /* ---- the three 7x7 stems, fused --------------------------------------------------
  * Replaces DLA.forward's base_layer / pre_img_layer / pre_hm_layer and their sum

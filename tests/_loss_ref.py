@@ -1,0 +1,219 @@
+"""The training loss as plain torch formulas on RAW head outputs, in whatever dtype the inputs have (float64 for the
+truth of the tests, float32 as the composed-from-torch-ops baseline of tools/loss_bench.py).  Written from the formulas
+the kernels implement (include/centertrack_hip.h); tests/test_losses_cpu.py pins it to the
+reference's own numbers (tests/golden/losses.npz).  No GPU code, no ctypes.
+
+A batch is a dict with the reference's keys (hm, ind, mask, cat, reg, reg_mask, ..., hp_ind, hm_hp_mask, joint, rotbin,
+rotres, rot_mask); ``outputs`` maps head -> logits [B,C,H,W]."""
+import math
+import os
+
+import numpy as np
+import torch
+
+L1_HEADS = ('reg', 'wh', 'tracking', 'ltrb', 'ltrb_amodal', 'hps', 'dim', 'amodel_offset', 'velocity', 'hp_offset')
+ALL_HEADS = ('hm', 'reg', 'wh', 'tracking', 'ltrb_amodal', 'dep', 'rot', 'dim', 'amodel_offset', 'nuscenes_att', 'velocity')
+HEAD_CH = {'hm': None, 'hm_hp': 17, 'reg': 2, 'wh': 2, 'tracking': 2, 'ltrb': 4, 'ltrb_amodal': 4, 'hps': 34, 'dep': 1,
+           'rot': 8, 'dim': 3, 'amodel_offset': 2, 'nuscenes_att': 8, 'velocity': 3, 'hp_offset': 2}
+
+
+def gather(x, ind):
+    """x [B,C,H,W], ind [B,M] -> x[b, :, ind[b, m]] as [B,M,C]"""
+    B, C = x.shape[:2]
+    return x.reshape(B, C, -1).permute(0, 2, 1).gather(1, ind.unsqueeze(2).expand(B, ind.shape[1], C))
+
+
+def focal(x, gt, ind, mask, cat):
+    p = torch.sigmoid(x).clamp(min=1e-4, max=1 - 1e-4)
+    neg = (torch.log(1 - p) * p ** 2 * (1 - gt) ** 4).sum()
+    pp = gather(p, ind).gather(2, cat.unsqueeze(2)).squeeze(2)
+    mask = mask.to(x.dtype)
+    pos = (torch.log(pp) * (1 - pp) ** 2 * mask).sum()
+    num_pos = mask.sum()
+    return -neg if float(num_pos) == 0 else -(pos + neg) / num_pos
+
+
+def weighted_l1(x, mask, ind, target, depth=False):
+    if depth:
+        x = 1. / (torch.sigmoid(x) + 1e-6) - 1.
+    mask = mask.to(x.dtype)
+    pred = gather(x, ind)
+    return (pred * mask - target * mask).abs().sum() / (mask.sum() + 1e-4)
+
+
+def weighted_bce(x, mask, ind, target):
+    z = gather(x, ind)
+    mask = mask.to(x.dtype)
+    bce = z.clamp(min=0) - z * target + torch.log1p(torch.exp(-z.abs()))
+    return (mask * bce).sum() / (mask.sum() + 1e-4)
+
+
+def _smooth_l1(d):
+    a = d.abs()
+    return torch.where(a < 1, 0.5 * d * d, a - 0.5)
+
+
+def bin_rot(x, mask, ind, rotbin, rotres):
+    """bin logits times the mask, cross-entropy mean over ALL rows; sin / cos smooth-L1 means over the rows with a non-zero
+    target bin, NOT masked; a residual term without such a row is 0"""
+    pred = gather(x, ind).reshape(-1, 8)
+    tb, tr, m = rotbin.reshape(-1, 2), rotres.reshape(-1, 2).to(x.dtype), mask.reshape(-1, 1).to(x.dtype)
+    loss = 0
+    for k in (0, 1):
+        z = pred[:, 4 * k:4 * k + 2] * m
+        loss = loss + (torch.logsumexp(z, 1) - z.gather(1, tb[:, k:k + 1]).squeeze(1)).mean()
+        rows = tb[:, k] != 0
+        if bool(rows.any()):
+            loss = loss + _smooth_l1(pred[rows, 4 * k + 2] - torch.sin(tr[rows, k])).mean()
+            loss = loss + _smooth_l1(pred[rows, 4 * k + 3] - torch.cos(tr[rows, k])).mean()
+    return loss
+
+
+def head_loss(head, x, batch):
+    if head == 'hm':
+        return focal(x, batch['hm'].to(x.dtype), batch['ind'], batch['mask'], batch['cat'])
+    if head == 'hm_hp':
+        return focal(x, batch['hm_hp'].to(x.dtype), batch['hp_ind'], batch['hm_hp_mask'], batch['joint'])
+    if head == 'rot':
+        return bin_rot(x, batch['rot_mask'], batch['ind'], batch['rotbin'], batch['rotres'])
+    ind = batch['hp_ind'] if head == 'hp_offset' else batch['ind']
+    if head == 'nuscenes_att':
+        return weighted_bce(x, batch[head + '_mask'], ind, batch[head].to(x.dtype))
+    return weighted_l1(x, batch[head + '_mask'], ind, batch[head].to(x.dtype), depth=head == 'dep')
+
+
+def generic_loss(outputs, batch, heads, weights, num_stacks=1):
+    """(tot, {head: loss}) of ``outputs`` = a list of num_stacks dicts"""
+    losses = {h: 0 for h in heads}
+    for s in range(num_stacks):
+        for h in heads:
+            if h in outputs[s]:
+                losses[h] = losses[h] + head_loss(h, outputs[s][h], batch) / num_stacks
+    tot = 0
+    for h in heads:
+        tot = tot + weights[h] * losses[h]
+    return tot, losses
+
+
+def losses_and_grads(outputs, batch, heads, dtype=torch.float64, device=None):
+    """per head (loss, d loss / d logits) in ``dtype`` from fp32 inputs"""
+    res = {}
+    for h in heads:
+        x = outputs[h].detach().to(device=device or outputs[h].device, dtype=dtype).requires_grad_()
+        b = {k: (v.to(device=x.device, dtype=dtype) if v.is_floating_point() else v.to(x.device)) for k, v in batch.items()}
+        loss = head_loss(h, x, b)
+        g, = torch.autograd.grad(loss, x)
+        res[h] = (loss.detach(), g)
+    return res
+
+
+def terms(head, x_shape, M):
+    """K, the number of summed terms behind a loss: B*C*H*W for a focal head, B*M*C for a slot head"""
+    B, C, H, W = x_shape
+    return B * C * H * W if head in ('hm', 'hm_hp') else B * M * C
+
+
+def err(a, ref, norm=None):
+    """the measure of tests/_dcn_bwd.py: max error over the largest reference magnitude"""
+    ref = ref.double()
+    n = float(ref.abs().max()) if norm is None else norm
+    return float((a.double().cpu() - ref.cpu()).abs().max()) / (n if n > 0 else 1.0)
+
+
+def bound(e32, K):
+    return min(1e-3, 4.0 * max(e32, 2.0 ** -23 * math.sqrt(K)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# seeded inputs
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def away_from_clamp(x, margin=1e-3, edge=9.2102):
+    """push logits that lie within ``margin`` of +-edge (where clamp(sigmoid(x), 1e-4, 1 - 1e-4) starts to act) out of
+    that band, so that float32 and float64 agree on which side they fall"""
+    for e in (edge, -edge):
+        near = (x - e).abs() < 2 * margin
+        x = torch.where(near, torch.full_like(x, e + 4 * margin), x)
+    return x
+
+
+def make_batch(seed, B, H, W, M, heads, num_classes, valid=None, scale=3.0, joints=17):
+    """(outputs {head: fp32 logits}, batch) with the reference's keys; ``valid[b]`` = objects of image b (default M // 2 + b)"""
+    g = _gen(seed)
+    HW = H * W
+    valid = [min(M, M // 2 + b) for b in range(B)] if valid is None else valid
+    mask = torch.zeros(B, M)
+    ind = torch.zeros(B, M, dtype=torch.int64)
+    cat = torch.zeros(B, M, dtype=torch.int64)
+    for b in range(B):
+        n = valid[b]
+        mask[b, :n] = 1
+        ind[b, :n] = torch.randint(0, HW, (n,), generator=g)
+        cat[b, :n] = torch.randint(0, num_classes, (n,), generator=g)
+    batch = {'ind': ind, 'mask': mask, 'cat': cat}
+    outputs = {}
+    for h in heads:
+        C = num_classes if h == 'hm' else HEAD_CH[h]
+        outputs[h] = away_from_clamp(torch.randn(B, C, H, W, generator=g) * scale)
+        if h == 'hm':
+            hm = torch.rand(B, C, H, W, generator=g) ** 4
+            for b in range(B):
+                for m in range(valid[b]):
+                    hm[b, cat[b, m], ind[b, m] // W, ind[b, m] % W] = 1
+            batch['hm'] = hm
+        elif h == 'hm_hp':
+            hp_mask = (torch.rand(B, M, joints, generator=g) < 0.7).float() * mask.unsqueeze(2)
+            hp_ind = torch.randint(0, HW, (B, M, joints), generator=g) * hp_mask.long()
+            batch['hp_ind'] = hp_ind.reshape(B, M * joints)
+            batch['hm_hp_mask'] = hp_mask.reshape(B, M * joints)
+            batch['joint'] = torch.arange(joints).repeat(B, M).reshape(B, M * joints)
+            hm = torch.rand(B, joints, H, W, generator=g) ** 4
+            bi = torch.arange(B).view(B, 1).expand(B, M * joints)
+            sel = batch['hm_hp_mask'] > 0
+            hm[bi[sel], batch['joint'][sel], batch['hp_ind'][sel] // W, batch['hp_ind'][sel] % W] = 1
+            batch['hm_hp'] = hm
+        elif h == 'hp_offset':
+            if 'hm_hp_mask' not in batch:
+                raise ValueError('list hm_hp before hp_offset')
+            batch['hp_offset'] = torch.rand(B, M * joints, 2, generator=g)
+            batch['hp_offset_mask'] = batch['hm_hp_mask'].unsqueeze(2).expand(B, M * joints, 2).contiguous()
+        elif h == 'rot':
+            batch['rotbin'] = torch.randint(0, 2, (B, M, 2), generator=g)     # (not masked: the residual terms are not either)
+            batch['rotres'] = (torch.rand(B, M, 2, generator=g) - 0.5) * 3
+            batch['rot_mask'] = mask.clone()
+        elif h == 'nuscenes_att':
+            batch[h] = (torch.rand(B, M, 8, generator=g) < 0.3).float()
+            batch[h + '_mask'] = (torch.rand(B, M, 8, generator=g) < 0.5).float() * mask.unsqueeze(2)
+        else:
+            C = HEAD_CH[h]
+            batch[h] = torch.randn(B, M, C, generator=g) * 2
+            if h == 'dep':
+                batch[h] = batch[h].abs() * 10 + 1
+            batch[h + '_mask'] = mask.unsqueeze(2).expand(B, M, C).contiguous()
+    return outputs, batch
+
+
+class Opt(object):
+    def __init__(self, heads, weights=None, num_stacks=1):
+        self.heads = {h: 0 for h in heads}
+        self.weights = {h: (0.1 if h == 'wh' else 1.0) for h in heads}
+        if weights:
+            self.weights.update(weights)
+        self.num_stacks = num_stacks
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/losses.npz
+
+CASES = ('A', 'B', 'C')
+
+
+def load_case(golden_dir, name):
+    z = np.load(os.path.join(golden_dir, 'losses.npz'))
+    heads = str(z['%s/heads' % name].reshape(-1)[0]).split(',')
+    pick = lambda prefix: {k[len(prefix):]: torch.from_numpy(z[k]) for k in z.files if k.startswith(prefix)}
+    return dict(heads=heads, out=pick('%s/out/' % name), batch=pick('%s/batch/' % name), loss=pick('%s/loss/' % name),
+                grad=pick('%s/grad/' % name), e32_loss=pick('%s/e32_loss/' % name), e32_grad=pick('%s/e32_grad/' % name))
