@@ -20,6 +20,12 @@ autograd enabled they return tensors with a ``grad_fn`` whose backward is ``ct_d
 (gradients for input, offset, mask, weight and bias).  The input gradient is
 accumulated with float atomics and is equal from run to run only to fp32 rounding; the other
 four are bitwise reproducible.
+
+The modules keep no packed copy of their parameters: ``weight`` (and ``conv_offset_mask.weight``) are packed into the
+MFMA fragment layouts at every call, from the values the storage holds at that moment.  A parameter may therefore be
+changed by any means between two calls -- an optimizer step, ``load_state_dict``, ``nn.init``, or a write through
+``.data`` (``m.weight.data.mul_(2)``, ``w = m.weight.data; w[...] = ...``, as the reference's ``fill_up_weights`` and
+many checkpoint loaders do), which does not advance the parameter's version counter -- and the next call uses it.
 """
 import contextlib
 import math
@@ -92,7 +98,8 @@ def _differentiable():
 
 class _DCNv2Function(torch.autograd.Function):
     """``ct_dcn_v2`` forward (the inference kernel, unchanged) + ``ct_dcn_v2_backward``.  ``packs`` = the (forward,
-    transposed) fragment packings of ``weight`` when the caller caches them, else None."""
+    transposed) fragment packings of ``weight`` when the caller has made them (the modules, at every call), else None:
+    the transposed one is then made in backward."""
 
     @staticmethod
     def forward(ctx, input, offset, mask, weight, bias, packs):
@@ -154,7 +161,6 @@ class DCNv2(nn.Module):
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
         self.bias = nn.Parameter(torch.empty(out_channels))
         self.reset_parameters()
-        self._packed = {}
 
     def reset_parameters(self):
         n = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
@@ -162,17 +168,12 @@ class DCNv2(nn.Module):
         self.weight.data.uniform_(-stdv, stdv)
         self.bias.data.zero_()
 
-    def _pack(self, name, t, pack=ops.pack_weight):
-        """MFMA-fragment packing of a weight, redone only when the parameter changes."""
-        key = (t.data_ptr(), t._version, t.device)
-        hit = self._packed.get(name)
-        if hit is None or hit[0] != key:
-            hit = (key, pack(t.detach()))
-            self._packed[name] = hit
-        return hit[1]
-
     def _packs(self):
-        return self._pack('weight', self.weight), self._pack('weight_t', self.weight, ops.pack_weight_t)
+        """(forward, transposed) MFMA-fragment packings of ``weight``, made from its current values at every call: one
+        small launch each on the caller's stream.  Nothing is cached: a write through ``weight.data`` changes the storage
+        without advancing the parameter's version counter, so no key built from ``data_ptr`` and ``_version`` sees it."""
+        w = self.weight.detach()
+        return ops.pack_weight(w), ops.pack_weight_t(w)
 
     def forward(self, input, offset, mask):
         _need_cuda(input)
@@ -184,7 +185,7 @@ class DCNv2(nn.Module):
     def _forward_inference(self, input, offset, mask):
         x = ops.view_from_nchw(input)
         om = _om_view(offset.float(), mask.float())
-        out = ops.dcn_v2(x, om, self._pack('weight', self.weight), self.out_channels, shift=self.bias.detach())
+        out = ops.dcn_v2(x, om, ops.pack_weight(self.weight.detach()), self.out_channels, shift=self.bias.detach())
         return ops.view_to_nchw(out)
 
 
@@ -220,9 +221,9 @@ class DCN(DCNv2):
         B, H, W = x.N, x.H, x.W
         # ``o1, o2, mask = chunk(out, 3, 1); offset = cat(o1, o2)`` is out[:, :18]; the sigmoid of
         # channels 18..26 is fused into the conv epilogue
-        om = ops.conv2d(x, self._pack('w_off', self.conv_offset_mask.weight), 27, 3, 1,
+        om = ops.conv2d(x, ops.pack_weight(self.conv_offset_mask.weight.detach()), 27, 3, 1,
                         shift=self.conv_offset_mask.bias.detach(), sig=(18, 27),
                         out=ops.new_view(B, H, W, 32, input.device))
-        out = ops.dcn_v2(x, ops.View(om.buf, 0, 27), self._pack('weight', self.weight), self.out_channels,
+        out = ops.dcn_v2(x, ops.View(om.buf, 0, 27), ops.pack_weight(self.weight.detach()), self.out_channels,
                          shift=self.bias.detach())
         return ops.view_to_nchw(out)

@@ -156,7 +156,7 @@ def make_batch(seed, B, H, W, M, heads, num_classes, valid=None, scale=3.0, join
     batch = {'ind': ind, 'mask': mask, 'cat': cat}
     outputs = {}
     for h in heads:
-        C = num_classes if h == 'hm' else HEAD_CH[h]
+        C = num_classes if h == 'hm' else joints if h == 'hm_hp' else HEAD_CH[h]
         outputs[h] = away_from_clamp(torch.randn(B, C, H, W, generator=g) * scale)
         if h == 'hm':
             hm = torch.rand(B, C, H, W, generator=g) ** 4
@@ -203,6 +203,115 @@ class Opt(object):
         if weights:
             self.weights.update(weights)
         self.num_stacks = num_stacks
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# training scale: the inputs of tests/test_hip_losses_scale.py, shared with the CPU checks of tests/test_losses_cpu.py
+
+DENSE_THREADS = 256                      # LOSS_DENSE_THREADS of csrc/loss.hip
+MAX_PARTIALS = 1024                      # LOSS_MAX_PARTIALS
+TRIP = 4 * DENSE_THREADS * MAX_PARTIALS  # elements one trip of the capped grid covers on the float4 path (1,048,576)
+CAP = 4 * TRIP                           # loss_plan gives a workgroup 4 trips; above 4,194,304 elements the grid stays 1024
+MAX_SLOTS = 8192                         # CT_LOSS_MAX_SLOTS of include/centertrack_hip.h
+SCALE = (2, 80, 128, 208, 16)            # B, C, H, W, M: 4,259,840 elements, the smallest COCO-like map above CAP
+SHARE_TOL = 1.0 / (8 * MAX_PARTIALS)     # the loss bound that sees one lost or doubled partial
+FIFTEEN = ('hm', 'reg', 'wh', 'tracking', 'ltrb', 'ltrb_amodal', 'dep', 'rot', 'dim', 'amodel_offset', 'nuscenes_att',
+           'velocity', 'hm_hp', 'hps', 'hp_offset')
+
+_scale_cache = {}
+
+
+def _once(key, make):
+    if key not in _scale_cache:
+        _scale_cache[key] = make()
+    return _scale_cache[key]
+
+
+def loss_err(got, want):
+    """relative; a zero truth wants a zero"""
+    got, want = float(got), float(want)
+    if want == 0.0:
+        return 0.0 if got == 0.0 else float('inf')
+    return abs(got - want) / abs(want)
+
+
+def truth_and_e32(key, out, batch, heads):
+    """({head: (loss, grad)} in float64, {head: (loss error, gradient error)} of the float32 mirror), once per process"""
+    def make():
+        w64 = losses_and_grads(out, batch, heads, torch.float64)
+        w32 = losses_and_grads(out, batch, heads, torch.float32)
+        return w64, {h: (loss_err(w32[h][0], w64[h][0]), err(w32[h][1], w64[h][1])) for h in heads}
+    return _once(('truth', key), make)
+
+
+def scale_batch():
+    """A1: random logits and targets above the partial cap"""
+    B, C, H, W, M = SCALE
+    return _once('scale', lambda: make_batch(41, B, H, W, M, ('hm',), C))
+
+
+def positive_elements(batch, shape):
+    """flat element indices of the positives (b, cat, ind) of a focal head of ``shape`` = [B,C,H,W]"""
+    B, C, H, W = shape
+    b = torch.arange(B).view(B, 1).expand_as(batch['ind'])
+    sel = batch['mask'] > 0
+    return ((b[sel] * C + batch['cat'][sel]) * (H * W) + batch['ind'][sel]).tolist()
+
+
+def partial_shares(x, batch, vec):
+    """float64 [MAX_PARTIALS]: the part of the loss that each workgroup's partial of loss_dense_fwd_kernel carries, i.e.
+    partial / (pos + neg).  Element i belongs to workgroup (i // 4 // 256) % 1024 on the float4 path and to
+    (i // 256) % 1024 on the scalar path (more than CAP elements, so the grid is capped at 1024)."""
+    n = x.numel()
+    assert n % 4 == 0 and n > CAP
+    xd, gt = x.double(), batch['hm'].double()
+    p = torch.sigmoid(xd).clamp(min=1e-4, max=1 - 1e-4)
+    t = (torch.log(1 - p) * p ** 2 * (1 - gt) ** 4).reshape(-1)
+    i = torch.arange(n)
+    wg = ((i // 4 if vec else i) // DENSE_THREADS) % MAX_PARTIALS
+    part = torch.zeros(MAX_PARTIALS, dtype=torch.float64).index_add_(0, wg, t)
+    pp = gather(p, batch['ind']).gather(2, batch['cat'].unsqueeze(2)).squeeze(2)
+    pos = (torch.log(pp) * (1 - pp) ** 2 * batch['mask'].double()).sum()
+    assert abs(float(part.sum() - t.sum())) <= 1e-9 * abs(float(t.sum()))
+    return part / (pos + t.sum())
+
+
+def scale_shares(vec):
+    out, batch = scale_batch()
+    return _once(('shares', vec), lambda: partial_shares(out['hm'], batch, vec))
+
+
+def probe_indices(n):
+    """A2: both ends, the elements beside the first and the last float4, both sides of every trip boundary, the middle"""
+    S = TRIP
+    return [0, 3, 4, n - 1, n - 4, n - 5, S - 1, S, S + 1, 3 * S - 1, 3 * S, n // 2]
+
+
+def probe_batch():
+    """A2: the inputs of A1 with a target of 1 everywhere but at the 12 probes (target 0): every other negative term is
+    exactly 0, so the loss is the 12 probe terms and the positives.  Probe k has the logit 0.5 + k / 4: twelve different
+    terms between 0.37 and 4.5, each a visible part of the loss, so that a lost probe is not made up for by a doubled one"""
+    def make():
+        out, batch = scale_batch()
+        probes = probe_indices(out['hm'].numel())
+        x = out['hm'].clone()
+        x.view(-1)[probes] = 0.5 + 0.25 * torch.arange(len(probes))
+        hm = torch.ones_like(batch['hm'])
+        hm.view(-1)[probes] = 0
+        return {'hm': x}, dict(batch, hm=hm), probes
+    return _once('probes', make)
+
+
+def slot_limit_batch():
+    """A3: hp_ind with M = 512 * 16 = MAX_SLOTS slots over 16 * 24 = 384 positions, (nearly) every object valid: a position
+    is named by about 15 live slots spread over the 32 scatter workgroups of its image, and position 0 by the masked ones"""
+    heads = ('hm', 'reg', 'hm_hp', 'hp_offset')
+    return _once('slots', lambda: make_batch(43, 2, 16, 24, 512, heads, 3, valid=[512, 509], joints=16) + (heads,))
+
+
+def fifteen_batch():
+    """A4: every head of losses.KNOWN_HEADS"""
+    return _once('fifteen', lambda: make_batch(44, 2, 8, 12, 8, FIFTEEN, 3))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -51,6 +51,83 @@ def test_mirror_reproduces_the_reference_in_float64(golden_dir, name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the inputs of tests/test_hip_losses_scale.py: what the GPU tests rely on, checked without a GPU
+
+def _float32_mirror_is_inside_the_bounds(want, e32, heads, terms):
+    """the float32 composition of the same formulas passes the check the kernels are held to: its own errors are finite
+    and below the cap of 1e-3 at which ``bound`` stops following e32"""
+    for h in heads:
+        assert e32[h][0] <= R.bound(e32[h][0], terms[h]), (h, 'loss', e32[h][0])
+        assert e32[h][1] <= R.bound(e32[h][1], 1), (h, 'grad', e32[h][1])
+        assert float(want[h][1].abs().max()) > 0, h
+
+
+def test_scale_inputs_every_partial_carries_more_than_twice_the_tolerance():
+    out, batch = R.scale_batch()
+    B, C, H, W, M = R.SCALE
+    n = out['hm'].numel()
+    assert tuple(out['hm'].shape) == (B, C, H, W) and n == 4259840 and R.CAP == 4194304 and R.CAP < n and n % R.TRIP
+    want, e32 = R.truth_and_e32('scale', out, batch, ('hm',))
+    _float32_mirror_is_inside_the_bounds(want, e32, ('hm',), {'hm': n})
+    tol = min(R.bound(e32['hm'][0], n), R.SHARE_TOL)
+    assert e32['hm'][0] <= tol
+    for vec in (True, False):
+        shares = R.scale_shares(vec)
+        print('loss scale cpu %s path: shares min %.3e max %.3e, e32 loss %.3e grad %.3e, tolerance %.3e'
+              % ('float4' if vec else 'scalar', float(shares.min()), float(shares.max()), e32['hm'][0], e32['hm'][1], tol))
+        assert shares.shape == (R.MAX_PARTIALS,) and 0.99 < float(shares.sum()) < 1      # (the positives are the rest)
+        assert tol < 0.5 * float(shares.min())
+        # the project bound alone would not do: it is as large as a whole share
+        assert R.bound(e32['hm'][0], n) > 0.5 * float(shares.min())
+
+
+def test_scale_probes_miss_the_positives_and_carry_the_whole_negative_sum():
+    out, batch, probes = R.probe_batch()
+    B, C, H, W, M = R.SCALE
+    n, S = out['hm'].numel(), R.TRIP
+    assert probes == [0, 3, 4, n - 1, n - 4, n - 5, S - 1, S, S + 1, 3 * S - 1, 3 * S, n // 2]
+    assert len(set(probes)) == 12 and all(0 <= p < n for p in probes)
+    pos = R.positive_elements(batch, out['hm'].shape)
+    assert len(pos) == len(set(pos)) == int(batch['mask'].sum()) == 17 and not set(pos) & set(probes)
+    assert int((batch['hm'] == 0).sum()) == 12 and int((batch['hm'] == 1).sum()) == n - 12
+    want, e32 = R.truth_and_e32('probes', out, batch, ('hm',))
+    K = len(probes) + B * M
+    _float32_mirror_is_inside_the_bounds(want, e32, ('hm',), {'hm': K})
+    g = want['hm'][1].reshape(-1)
+    live = torch.zeros(n, dtype=torch.bool)
+    live[probes + pos] = True
+    assert float(g[~live].abs().max()) == 0.0 and bool((g[probes] != 0).all())          # no probe sits in the clamp
+    # every probe is a visible part of the loss: losing or doubling one moves it by far more than the bound
+    x, mask = out['hm'].double().reshape(-1)[probes], float(batch['mask'].sum())
+    p = torch.sigmoid(x)
+    each = -(torch.log(1 - p) * p ** 2) / mask / float(want['hm'][0])
+    print('loss probes cpu: smallest probe share of the loss %.3e, bound %.3e' % (float(each.min()), R.bound(e32['hm'][0], K)))
+    assert float(each.min()) > 1e-3 > 100 * R.bound(e32['hm'][0], K) and len(set(each.tolist())) == 12
+
+
+def test_slot_limit_and_fifteen_head_inputs():
+    out, batch, heads = R.slot_limit_batch()
+    assert heads == ('hm', 'reg', 'hm_hp', 'hp_offset') and tuple(out['hm_hp'].shape) == (2, 16, 16, 24)
+    assert batch['hp_ind'].shape == (2, R.MAX_SLOTS) and int(batch['hp_ind'].max()) < 16 * 24
+    # every position is named by many slots of either image
+    for b in (0, 1):
+        live = batch['hp_ind'][b][batch['hm_hp_mask'][b] > 0]
+        assert live.numel() > 5000 and torch.bincount(live, minlength=384).min() >= 4
+        assert int((batch['hp_ind'][b] == 0).sum()) > 2000            # the masked slots all name position 0
+    want, e32 = R.truth_and_e32('slots', out, batch, heads)
+    M = {'hm': 512, 'reg': 512, 'hm_hp': R.MAX_SLOTS, 'hp_offset': R.MAX_SLOTS}
+    _float32_mirror_is_inside_the_bounds(want, e32, heads, {h: R.terms(h, out[h].shape, M[h]) for h in heads})
+    from centertrack_amd import losses
+    out, batch = R.fifteen_batch()
+    assert sorted(R.FIFTEEN) == sorted(losses.KNOWN_HEADS) and list(out) == list(R.FIFTEEN)
+    assert tuple(out['ltrb'].shape) == (2, 4, 8, 12) and tuple(out['hps'].shape) == (2, 34, 8, 12)
+    assert batch['hps'].shape == batch['hps_mask'].shape == (2, 8, 34) and batch['hp_ind'].shape == (2, 8 * 17)
+    want, e32 = R.truth_and_e32('fifteen', out, batch, R.FIFTEEN)
+    terms = {h: R.terms(h, out[h].shape, 8 * 17 if h in ('hm_hp', 'hp_offset') else 8) for h in R.FIFTEEN}
+    _float32_mirror_is_inside_the_bounds(want, e32, R.FIFTEEN, terms)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # host-side validation (no GPU: nothing is launched for a rejected descriptor)
 
 @pytest.fixture(scope='module')
