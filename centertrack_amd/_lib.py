@@ -95,6 +95,32 @@ class LossDesc(ctypes.Structure):
                 ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
 
 
+CT_HEADS_BWD_HIDDEN, CT_HEADS_BWD_WEIGHT = 1, 2
+
+
+class ConvBwdWeightDesc(ctypes.Structure):
+    _fields_ = [('x', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('Cin', ctypes.c_int), ('ldx', ctypes.c_int),
+                ('gy', ctypes.c_void_p), ('Cout', ctypes.c_int), ('ldgy', ctypes.c_int),
+                ('ks', ctypes.c_int), ('stride', ctypes.c_int),
+                ('gw', ctypes.c_void_p), ('gb', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
+class HeadsTailHead(ctypes.Structure):
+    _fields_ = [('gout', ctypes.c_void_p), ('c', ctypes.c_int), ('w2', ctypes.c_void_p),
+                ('gw2', ctypes.c_void_p), ('gb2', ctypes.c_void_p)]
+
+
+class HeadsTailBwdDesc(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int), ('hc', ctypes.c_int),
+                ('heads', ctypes.POINTER(HeadsTailHead)), ('nheads', ctypes.c_int),
+                ('mid', ctypes.c_void_p), ('ldmid', ctypes.c_int),
+                ('gmid', ctypes.c_void_p), ('ldgmid', ctypes.c_int),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+                ('flags', ctypes.c_int)]
+
+
 CT_MAX_FUSED_HEADS = 8
 
 
@@ -201,7 +227,9 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_packed_winograd_elems', 'ct_pack_winograd_weight', 'ct_conv2d',
            'ct_conv2d_workspace_bytes', 'ct_heads_fused', 'ct_dcn_v2', 'ct_dcn_v2_workspace_bytes', 'ct_dcn_v2_offsets_bytes', 'ct_dcn_v2_group', 'ct_dcn_v2_group_workspace_bytes', 'ct_dcn_v2_group_plan',
            'ct_dcn_v2_backward', 'ct_dcn_v2_backward_workspace_bytes', 'ct_packed_dcn_weight_t_elems', 'ct_pack_dcn_weight_t',
-           'ct_generic_loss_forward', 'ct_generic_loss_backward', 'ct_generic_loss_workspace_bytes', 'ct_stem_forward',
+           'ct_generic_loss_forward', 'ct_generic_loss_backward', 'ct_generic_loss_workspace_bytes',
+           'ct_conv2d_backward_weight', 'ct_conv2d_backward_weight_workspace_bytes', 'ct_heads_tail_backward',
+           'ct_heads_tail_backward_workspace_bytes', 'ct_stem_forward',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
            'ct_decode_pose', 'ct_render_pre_hm',
@@ -271,6 +299,12 @@ def load():
     lib.ct_generic_loss_backward.argtypes = [ctypes.POINTER(LossDesc), p]
     lib.ct_generic_loss_workspace_bytes.restype = sz
     lib.ct_generic_loss_workspace_bytes.argtypes = [ctypes.POINTER(LossDesc)]
+    lib.ct_conv2d_backward_weight.argtypes = [ctypes.POINTER(ConvBwdWeightDesc), p]
+    lib.ct_conv2d_backward_weight_workspace_bytes.restype = sz
+    lib.ct_conv2d_backward_weight_workspace_bytes.argtypes = [ctypes.POINTER(ConvBwdWeightDesc)]
+    lib.ct_heads_tail_backward.argtypes = [ctypes.POINTER(HeadsTailBwdDesc), p]
+    lib.ct_heads_tail_backward_workspace_bytes.restype = sz
+    lib.ct_heads_tail_backward_workspace_bytes.argtypes = [ctypes.POINTER(HeadsTailBwdDesc)]
     lib.ct_stem_forward.argtypes = [p, p, p, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_stem_forward_parts.argtypes = [p, p, p, p, i, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_maxpool2x2.argtypes = [p, i, i, i, i, i, p, i, p]

@@ -1,0 +1,185 @@
+"""Trainable heads (reference ``BaseModel.__init__`` / ``forward``, src/lib/model/networks/base_model.py:24-65,86-90) on the
+HIP kernels: ``FusedHeads`` is the differentiable module, ``HeadFinetuner`` puts it on a frozen ``DLASegHIP`` trunk.
+
+Forward is the un-fused heads plan of ``model.DLASegHIP`` (one ``ct_conv2d`` 64 -> hc * nheads with bias and ReLU into an
+NHWC hidden map, one 1x1 ``ct_conv2d`` per head into NCHW logits); backward is ``ct_heads_tail_backward``,
+``ct_conv2d_backward_weight`` and, for the input gradient, a ``ct_conv2d`` with the transposed weight (csrc/heads_bwd.hip,
+DESIGN.md section 11).  No atomics: every gradient is bitwise equal from run to run.
+
+Like ``dcn_v2.DCN`` the module keeps no packed copy of a parameter: the weights are packed into the MFMA fragment layout
+at every call from what their storage holds at that moment, so an optimizer step, ``load_state_dict`` or a write through
+``.data`` is seen by the next call.  CUDA tensors only: a CPU tensor raises ``CTError``.
+"""
+from collections import OrderedDict
+
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib, ops
+
+
+def _one_head_conv(head_conv, heads):
+    """the single hidden width of all heads, from an int or the reference's {head: [256]}"""
+    if isinstance(head_conv, dict):
+        vals = {tuple(v) if isinstance(v, (list, tuple)) else (v,) for h, v in head_conv.items() if h in heads}
+    else:
+        vals = {tuple(head_conv) if isinstance(head_conv, (list, tuple)) else (head_conv,)}
+    if len(vals) != 1 or len(next(iter(vals))) != 1:
+        raise _lib.CTError('FusedHeads supports one head-conv layer of one width for all heads (got %r)' % (head_conv,))
+    hc = int(next(iter(vals))[0])
+    if hc <= 0 or hc % 16:
+        raise _lib.CTError('FusedHeads needs head_conv %% 16 == 0 (got %d)' % hc)
+    return hc
+
+
+class _HeadsFunction(torch.autograd.Function):
+    """(head names, feat, *(w0, b0, w2, b2 per head)) -> the heads' raw logits.  ``feat``: NCHW tensor or ``ops.View``."""
+
+    @staticmethod
+    def forward(ctx, names, feat, *params):
+        nh = len(names)
+        p = [t.detach() for t in params]
+        w0s, b0s = p[0::4], p[1::4]
+        w2s = OrderedDict(zip(names, p[2::4]))
+        b2s = OrderedDict(zip(names, p[3::4]))
+        grad = any(ctx.needs_input_grad)
+        if isinstance(feat, ops.View):
+            # what backward reads lives in storage private to this call: the caller's view is usually a buffer of a launch
+            # plan, rewritten by the next forward
+            need_feat = any(ctx.needs_input_grad[2 + 4 * j] or ctx.needs_input_grad[3 + 4 * j] for j in range(nh))
+            x = ops.View(feat.buf[..., feat.c0:feat.c0 + feat.C].clone(memory_format=torch.contiguous_format)) if need_feat else feat
+        else:
+            x = ops.view_from_nchw(feat.detach())
+        outs, mid = ops.heads_forward_train(x, torch.cat(w0s, 0), torch.cat(b0s, 0), w2s, b2s)
+        if grad:
+            ctx.names, ctx.x, ctx.mid = names, x, mid
+            ctx.save_for_backward(*params)
+        return tuple(outs.values())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gouts):
+        names, nh = ctx.names, len(ctx.names)
+        p = [t.detach() for t in ctx.saved_tensors]
+        need = ctx.needs_input_grad
+        hc = p[0].shape[0]
+        needs = {'x': need[1], 'w0': any(need[2 + 4 * j] for j in range(nh)), 'b0': any(need[3 + 4 * j] for j in range(nh)),
+                 'w2': {h: need[4 + 4 * j] for j, h in enumerate(names)}, 'b2': {h: need[5 + 4 * j] for j, h in enumerate(names)}}
+        w0 = torch.cat(p[0::4], 0) if needs['x'] else None
+        res = ops.heads_backward(ctx.x, ctx.mid, dict(zip(names, gouts)), w0, OrderedDict(zip(names, p[2::4])), needs)
+        grads = [None, ops.view_to_nchw(res['x']) if needs['x'] else None]
+        for j, h in enumerate(names):
+            grads += [res['w0'][hc * j:hc * (j + 1)] if need[2 + 4 * j] else None,
+                      res['b0'][hc * j:hc * (j + 1)] if need[3 + 4 * j] else None,
+                      res['w2'][h] if need[4 + 4 * j] else None, res['b2'][h] if need[5 + 4 * j] else None]
+        return tuple(grads)
+
+
+class FusedHeads(nn.Module):
+    """The heads of the reference's ``BaseModel`` as one differentiable module: per head ``conv3x3 in_channels -> head_conv
+    + bias, ReLU, conv1x1 head_conv -> c + bias``, parameters under the reference's names (``<head>.0.weight``,
+    ``<head>.0.bias``, ``<head>.2.weight``, ``<head>.2.bias``) and with its initialisation (base_model.py:54-57: torch's
+    Conv2d default for the weights; biases 0; in a head whose name contains ``hm`` the last bias = ``prior_bias`` and, as
+    there, the first layer's bias keeps torch's default).
+
+    ``forward(feat)``: NCHW fp32 CUDA tensor [B,in_channels,H,W] or an ``ops.View`` -> ``OrderedDict{head: raw logits
+    [B,c,H,W]}`` through ONE autograd function for all heads.  What is computed in backward follows ``requires_grad``: a
+    feature map that needs no gradient launches no input-gradient conv, frozen ``.0`` parameters launch no weight-gradient
+    kernel."""
+
+    def __init__(self, heads, head_conv=256, in_channels=64, prior_bias=-4.6):
+        super().__init__()
+        self.heads = OrderedDict(heads)
+        self.head_conv = _one_head_conv(head_conv, self.heads)
+        self.in_channels = in_channels
+        if not self.heads or len(self.heads) > _lib.CT_LOSS_MAX_HEADS:
+            raise _lib.CTError('FusedHeads takes 1 .. %d heads (got %d)' % (_lib.CT_LOSS_MAX_HEADS, len(self.heads)))
+        if in_channels % 16:
+            raise _lib.CTError('FusedHeads needs in_channels %% 16 == 0 (got %d)' % in_channels)
+        for h, c in self.heads.items():
+            # containers of the parameters only (never called): the reference's module tree, so names and default
+            # initialisation are torch's own
+            fc = nn.Sequential(nn.Conv2d(in_channels, self.head_conv, 3, padding=1, bias=True), nn.ReLU(inplace=True),
+                               nn.Conv2d(self.head_conv, c, 1, bias=True))
+            if 'hm' in h:
+                fc[-1].bias.data.fill_(prior_bias)
+            else:
+                for m in fc.modules():
+                    if isinstance(m, nn.Conv2d) and m.bias is not None:
+                        nn.init.constant_(m.bias, 0)
+            self.add_module(h, fc)
+
+    def head_parameters(self, h):
+        fc = getattr(self, h)
+        return fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias
+
+    def forward(self, feat):
+        if isinstance(feat, ops.View):
+            dev, cin = feat.buf.device, feat.C
+        elif torch.is_tensor(feat) and feat.dim() == 4:
+            dev, cin = feat.device, feat.shape[1]
+            if feat.dtype != torch.float32:
+                raise _lib.CTError('FusedHeads computes in fp32 (got %s)' % feat.dtype)
+        else:
+            raise _lib.CTError('FusedHeads takes an NCHW tensor or an ops.View')
+        if dev.type != 'cuda':
+            raise _lib.CTError('FusedHeads runs on an MI355X only (got a %s tensor); no CPU fallback' % dev)
+        if cin != self.in_channels:
+            raise _lib.CTError('FusedHeads was built for %d input channels (got %d)' % (self.in_channels, cin))
+        params = [t for h in self.heads for t in self.head_parameters(h)]
+        outs = _HeadsFunction.apply(tuple(self.heads), feat, *params)
+        return OrderedDict(zip(self.heads, outs))
+
+
+class HeadFinetuner(nn.Module):
+    """Fine-tuning of the heads of a ``DLASegHIP`` on its frozen trunk -- the workflow of the reference's ``load_model``
+    with ``reset_hm`` / ``reuse_hm`` or a new class count (model.py:49-63).  The trunk runs under ``no_grad`` on the
+    inference kernels up to the 64-channel feature map; the heads are a ``FusedHeads`` initialised from the model's current
+    head tensors.  ``parameters()`` yields the head parameters only; the model's own inference path does not change until
+    ``commit()`` writes them back."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+        dev = next(model.buffers()).device
+        self.heads = FusedHeads(model.heads, model.head_conv).to(dev)
+        sd = model.state_dict()
+        self.heads.load_state_dict(OrderedDict((k, sd[k]) for k in self.heads.state_dict()))
+
+    def forward(self, x, pre_img=None, pre_hm=None):
+        """the reference's signature (base_model.py:73): ``[{head: raw logits with a grad_fn}]``"""
+        m = self.model
+        if pre_img is not None and not m.pre_img:
+            raise _lib.CTError('model was built with pre_img=False')
+        if pre_hm is not None and not m.pre_hm:
+            raise _lib.CTError('model was built with pre_hm=False')
+        N, _, H, W = x.shape
+        with torch.no_grad():
+            plan = m.get_plan(N, H, W, pre_img is not None, pre_hm is not None, trunk_only=True)
+            m.forward_plan(plan, x, pre_img, pre_hm)
+        z = self.heads(plan['feat'])
+        if m.model_output_list:
+            return [[z[h] for h in sorted(m.heads)]]
+        return [z]
+
+    @torch.no_grad()
+    def commit(self):
+        """write the head parameters back into the model's buffers: the next inference forward, a ``Detector`` built
+        afterwards and the model's ``state_dict()`` see them"""
+        for k, v in self.heads.state_dict().items():
+            getattr(self.model, k.replace('.', '__')).copy_(v)
+        self.model._prepared = None
+        self.model._plans = {}
+
+    def state_dict(self, *a, **k):
+        """the full reference-format dict: trunk buffers + the current head parameters"""
+        sd = self.model.state_dict()
+        own = self.heads.state_dict()
+        return OrderedDict((n, own[n].detach() if n in own else v) for n, v in sd.items())
+
+    def load_state_dict(self, sd, strict=True):
+        own = self.heads.state_dict()
+        res = self.model.load_state_dict(sd, strict=strict)
+        self.heads.load_state_dict(OrderedDict((n, sd[n]) for n in own if n in sd), strict=strict)
+        return res

@@ -54,7 +54,8 @@ class _DcnLayer(object):
 
 
 class DLASegHIP(torch.nn.Module):
-    """Drop-in for the reference ``DLASeg(34, heads, head_convs, opt)`` at inference."""
+    """Drop-in for the reference ``DLASeg(34, heads, head_convs, opt)`` at inference.  Its heads can be fine-tuned on the
+    frozen trunk through ``heads.HeadFinetuner``; the trunk has no backward."""
 
     def __init__(self, heads, head_conv=256, pre_img=True, pre_hm=True, depth_scale=1.0,
                  model_output_list=False):
@@ -225,7 +226,9 @@ class DLASegHIP(torch.nn.Module):
         self._prepared = P
         return P
 
-    def _build_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads=False):
+    def _build_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads=False, *, trunk_only=False):
+        """``trunk_only``: the plan stops at ``plan['feat']``, the 64-channel feature map, and has no head launches
+        (heads.HeadFinetuner trains the heads on it)"""
         P = self._prepare()
         lib = _lib.load()
         dev = next(self.buffers()).device
@@ -377,7 +380,11 @@ class DLASegHIP(torch.nn.Module):
             small = [h for h in small if ('sparse.' + h) not in P]          # (the dead heads leave the dense launch too)
             if any(('sparse.' + h) in P for h in big):          # (more small heads than one fused launch holds: not with sparse heads)
                 raise _lib.CTError('sparse heads: %s do not fit the fused-heads launch' % [h for h in big if ('sparse.' + h) in P])
-        if small or plan['sparse'] is not None:
+        if trunk_only:
+            if sparse_heads:
+                raise _lib.CTError('a trunk-only plan has no heads, sparse or dense')
+            outputs = OrderedDict()
+        elif small or plan['sparse'] is not None:
             outputs = self._plan_heads_fused(plan, L, P, feat, N, dev, tune, fuse_sigmoid, small, big)
         else:
             nh = len(self.heads)
@@ -828,10 +835,10 @@ class DLASegHIP(torch.nn.Module):
                 parts.append('%s:%s' % (l.name, l.fn))
         return ';'.join(parts)
 
-    def get_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid=False, sparse_heads=False):
-        key = (N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads)
+    def get_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid=False, sparse_heads=False, *, trunk_only=False):
+        key = (N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads, trunk_only)
         if key not in self._plans:
-            self._plans[key] = self._build_plan(*key)
+            self._plans[key] = self._build_plan(*key[:7], trunk_only=trunk_only)
         return self._plans[key]
 
     def forward_plan(self, plan, x, pre_img=None, pre_hm=None):

@@ -329,6 +329,153 @@ def generic_loss_backward(heads, grad_loss, needs=None):
     return grads
 
 
+def conv_backward_weight(x, gy, ks, need_bias=True):
+    """Weight (and bias) gradient of ``conv(x, w) + b`` (``ks`` 1 or 3, stride 1, pad ks // 2) for the output gradient ``gy``
+    (NHWC views) -> ``(gw OIHW [gy.C, x.C, ks, ks], gb [gy.C] or None)``.  Two launches, bitwise reproducible."""
+    lib = _lib.load()
+    dev = x.buf.device
+    if (x.N, x.H, x.W) != (gy.N, gy.H, gy.W):
+        raise _lib.CTError('conv_backward_weight: x is %s pixels, gy %s' % ((x.N, x.H, x.W), (gy.N, gy.H, gy.W)))
+    d = _lib.ConvBwdWeightDesc()
+    d.x, d.N, d.H, d.W, d.Cin, d.ldx = x.ptr, x.N, x.H, x.W, x.C, x.ld
+    d.gy, d.Cout, d.ldgy = gy.ptr, gy.C, gy.ld
+    d.ks, d.stride = ks, 1
+    need = lib.ct_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))
+    if not need:
+        raise _lib.CTError('ct_conv2d_backward_weight_workspace_bytes: %s' % lib.ct_last_error().decode())
+    gw = torch.empty((gy.C, x.C, ks, ks), dtype=torch.float32, device=dev)
+    gb = torch.empty(gy.C, dtype=torch.float32, device=dev) if need_bias else None
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    d.gw, d.gb = gw.data_ptr(), _p(gb)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    _lib.check(lib.ct_conv2d_backward_weight(ctypes.byref(d), _lib.stream_ptr()), 'ct_conv2d_backward_weight')
+    return gw, gb
+
+
+def _head_tensor(t, what):
+    if not t.is_cuda:
+        raise _lib.CTError('%s runs on an MI355X only (got a %s tensor); no CPU fallback' % (what, t.device))
+    if t.dtype != torch.float32:
+        raise _lib.CTError('%s computes in fp32 (got %s)' % (what, t.dtype))
+    return t.detach().contiguous()
+
+
+def heads_forward_train(feat, w0, b0, w2s, b2s):
+    """The heads (base_model.py:24-65) with the hidden map kept for a backward: ``feat`` NHWC view [N,H,W,Cin]; ``w0``
+    [nheads*hc, Cin, 3, 3] / ``b0`` [nheads*hc] = the heads' first layers concatenated in the order of ``w2s``; ``w2s`` /
+    ``b2s`` = {head: [c, hc(, 1, 1)]} / {head: [c]}.  -> (OrderedDict {head: raw logits NCHW [N,c,H,W]}, ``mid`` = the NHWC
+    view [N,H,W,nheads*hc] after the ReLU).  The un-fused heads plan of the model: one ct_conv2d into ``mid``, one per
+    head into its logits; the weights are packed here, from what their storage holds now."""
+    from collections import OrderedDict
+    nh = len(w2s)
+    w0, b0 = _head_tensor(w0, 'heads_forward_train'), _head_tensor(b0, 'heads_forward_train')
+    if nh == 0 or w0.shape[0] % nh or w0.shape[1] != feat.C or tuple(w0.shape[2:]) != (3, 3) or b0.numel() != w0.shape[0]:
+        raise _lib.CTError('heads_forward_train: w0 %s / b0 %s do not fit %d heads on %d channels'
+                           % (tuple(w0.shape), tuple(b0.shape), nh, feat.C))
+    hc = w0.shape[0] // nh
+    dev = feat.buf.device
+    mid = new_view(feat.N, feat.H, feat.W, hc * nh, dev)
+    conv2d(feat, pack_weight(w0), hc * nh, 3, 1, shift=b0, relu=True, out=mid)
+    out = OrderedDict()
+    for j, (h, w2) in enumerate(w2s.items()):
+        w2, b2 = _head_tensor(w2, 'heads_forward_train'), _head_tensor(b2s[h], 'heads_forward_train')
+        c = w2.shape[0]
+        if w2.numel() != c * hc or b2.numel() != c:
+            raise _lib.CTError('heads_forward_train: head %s: w2 %s / b2 %s with %d hidden channels'
+                               % (h, tuple(w2.shape), tuple(b2.shape), hc))
+        o = torch.empty((feat.N, c, feat.H, feat.W), dtype=torch.float32, device=dev)
+        conv2d(mid.slice(hc * j, hc), pack_weight(w2.reshape(c, hc, 1, 1)), c, 1, 1, shift=b2, out_nchw=o)
+        out[h] = o
+    return out, mid
+
+
+def make_heads_tail_desc(mid, gouts, w2s=None, gmid=None, gw2s=None, gb2s=None):
+    """``ct_heads_tail_bwd_desc`` over caller-owned buffers: ``gouts`` = [logit gradient NCHW] per head, ``w2s`` = [[c, hc]],
+    ``gw2s`` / ``gb2s`` = [buffer or None]; what is computed follows from the output buffers given.  Returns (descriptor,
+    keep-alive)."""
+    nh = len(gouts)
+    arr = (_lib.HeadsTailHead * max(nh, 1))()
+    for i, g in enumerate(gouts):
+        h = arr[i]
+        h.gout, h.c = g.data_ptr(), g.shape[1]
+        h.w2 = _p(w2s[i]) if w2s is not None else None
+        h.gw2 = _p(gw2s[i]) if gw2s is not None else None
+        h.gb2 = _p(gb2s[i]) if gb2s is not None else None
+    d = _lib.HeadsTailBwdDesc()
+    d.N, d.H, d.W, d.hc = mid.N, mid.H, mid.W, (mid.C // nh if nh else 0)
+    d.heads, d.nheads = arr, nh
+    d.mid, d.ldmid = mid.ptr, mid.ld
+    flags = 0
+    if gmid is not None:
+        d.gmid, d.ldgmid = gmid.ptr, gmid.ld
+        flags |= _lib.CT_HEADS_BWD_HIDDEN
+    if (gw2s is not None and any(t is not None for t in gw2s)) or (gb2s is not None and any(t is not None for t in gb2s)):
+        flags |= _lib.CT_HEADS_BWD_WEIGHT
+    d.flags = flags
+    return d, arr
+
+
+def heads_backward(feat, mid, gouts, w0, w2s, needs, gmid=None):
+    """Gradients of ``heads_forward_train`` for the logit gradients ``gouts`` = {head: [N,c,H,W]} (every head, in the order
+    of ``w2s``).  ``needs`` = {'x', 'w0', 'b0': bool, 'w2', 'b2': bool or {head: bool}}; missing keys are False.  Returns
+    {'x': view or None, 'w0': [nheads*hc,Cin,3,3] or None, 'b0', 'w2': {head: [c,hc,1,1] or None}, 'b2': {head: ...},
+    'gmid': the hidden gradient's view or None}: no buffer is allocated and no kernel runs for what was not asked for.
+    ``gmid``: a caller-owned view for the hidden gradient (any pitch).  ``feat`` may be None when neither 'w0' nor 'b0' is
+    needed.  Every result is bitwise reproducible."""
+    lib = _lib.load()
+    heads = list(w2s)
+    nh = len(heads)
+    dev = mid.buf.device
+    hc = mid.C // nh
+    if mid.C != hc * nh or sorted(gouts) != sorted(heads):
+        raise _lib.CTError('heads_backward: %d hidden channels / gradients %s for heads %s' % (mid.C, sorted(gouts), heads))
+
+    def per_head(v):
+        return {h: bool(v.get(h, False)) for h in heads} if isinstance(v, dict) else {h: bool(v) for h in heads}
+    need_x, need_w0, need_b0 = (bool(needs.get(k, False)) for k in ('x', 'w0', 'b0'))
+    need_w2, need_b2 = per_head(needs.get('w2', False)), per_head(needs.get('b2', False))
+    need_mid = need_x or need_w0 or need_b0
+    res = {'x': None, 'w0': None, 'b0': None, 'w2': {h: None for h in heads}, 'b2': {h: None for h in heads}, 'gmid': None}
+    g, w2 = [], []
+    for h in heads:
+        t = _head_tensor(gouts[h], 'heads_backward')
+        if t.dim() != 4 or (t.shape[0], t.shape[2], t.shape[3]) != (mid.N, mid.H, mid.W):
+            raise _lib.CTError('heads_backward: gradient of %s is %s on a %s map' % (h, tuple(t.shape), (mid.N, mid.H, mid.W)))
+        g.append(t)
+        w = _head_tensor(w2s[h], 'heads_backward')
+        if w.numel() != t.shape[1] * hc:
+            raise _lib.CTError('heads_backward: head %s: w2 %s for %d logit and %d hidden channels' % (h, tuple(w.shape), t.shape[1], hc))
+        w2.append(w)
+    gw2 = [torch.empty((t.shape[1], hc, 1, 1), dtype=torch.float32, device=dev) if need_w2[h] else None for h, t in zip(heads, g)]
+    gb2 = [torch.empty(t.shape[1], dtype=torch.float32, device=dev) if need_b2[h] else None for h, t in zip(heads, g)]
+    if need_mid:
+        if gmid is None:
+            gmid = new_view(mid.N, mid.H, mid.W, mid.C, dev)
+        elif (gmid.N, gmid.H, gmid.W, gmid.C) != (mid.N, mid.H, mid.W, mid.C):
+            raise _lib.CTError('heads_backward: the gmid view does not have the shape of mid')
+    else:
+        gmid = None
+    d, _keep = make_heads_tail_desc(mid, g, w2, gmid, gw2, gb2)
+    if d.flags:
+        need = lib.ct_heads_tail_backward_workspace_bytes(ctypes.byref(d))
+        if d.flags & _lib.CT_HEADS_BWD_WEIGHT:
+            if not need:
+                raise _lib.CTError('ct_heads_tail_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
+            ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+            d.workspace, d.workspace_bytes = ws.data_ptr(), need
+        _lib.check(lib.ct_heads_tail_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_heads_tail_backward')
+    res['w2'], res['b2'], res['gmid'] = dict(zip(heads, gw2)), dict(zip(heads, gb2)), gmid
+    if need_w0 or need_b0:
+        gw0, gb0 = conv_backward_weight(feat, gmid, 3, need_bias=need_b0)
+        res['w0'], res['b0'] = (gw0 if need_w0 else None), gb0
+    if need_x:
+        # conv3x3(gmid, w0^T): w0T[ci, co, ky, kx] = w0[co, ci, 2 - ky, 2 - kx], on the forward conv kernels
+        w0 = _head_tensor(w0, 'heads_backward')
+        w0t = w0.permute(1, 0, 2, 3).flip(2, 3).contiguous()
+        res['x'] = conv2d(gmid, pack_weight(w0t), w0.shape[1], 3, 1)
+    return res
+
+
 def stem(x, pre_img, pre_hm, w_x, w_img, w_hm, scale3, shift3, out=None):
     N, _, H, W = x.shape
     if out is None:

@@ -41,7 +41,9 @@ extern "C" {
  * diagnostics of the measuring box: tools/micro/probes.hip -> tools/micro/libct_probes.so; ct_dcn_desc.w_off_winograd).
  * Added under 103 without a layout change: ct_dcn_desc.algo 53264 / 532128 / 63264 / 632128 (persistent DCN launch), the
  * tuning keys "dcn_slots" and "dcn_xcd"; ct_dcn_bwd_desc and ct_dcn_v2_backward (a new descriptor and new symbols);
- * ct_loss_head / ct_loss_desc and ct_generic_loss_* (the training loss: new descriptors and new symbols). */
+ * ct_loss_head / ct_loss_desc and ct_generic_loss_* (the training loss: new descriptors and new symbols);
+ * ct_conv_bwd_weight_desc / ct_heads_tail_bwd_desc, ct_conv2d_backward_weight and ct_heads_tail_backward (the backward of
+ * the heads: new descriptors and new symbols). */
 #define CT_ABI_VERSION 103
 
 const char *ct_last_error(void);
@@ -298,6 +300,61 @@ typedef struct ct_loss_desc {
 int ct_generic_loss_forward(const ct_loss_desc *d, void *stream);
 int ct_generic_loss_backward(const ct_loss_desc *d, void *stream);
 size_t ct_generic_loss_workspace_bytes(const ct_loss_desc *d);   /* 0 for a rejected descriptor */
+
+/* ---- backward of the heads (base_model.py:24-65: per head conv3x3 64 -> hc + bias, ReLU, conv1x1 hc -> c + bias); additions
+ * under ABI 103.  The training forward is ct_conv2d twice (the un-fused heads plan: one 3x3 conv into an NHWC hidden map
+ * `mid` [N,H,W,nheads*hc] with bias and ReLU, one 1x1 conv per head into NCHW logits).  Backward, all fp32, no atomics, every
+ * result bitwise equal from run to run:
+ *   1. ct_heads_tail_backward: logit gradients -> hidden gradient gmid (through the ReLU), gw2, gb2
+ *   2. ct_conv2d_backward_weight(x = feature map, gy = gmid, ks = 3): gw0, gb0
+ *   3. the input gradient is ct_conv2d(gmid, ct_pack_conv_weight(w0T), Cout = Cin of the heads, ks = 3) with
+ *      w0T[ci][co][ky][kx] = w0[co][ci][2-ky][2-kx]: no new entry point.
+ *
+ * ct_conv2d_backward_weight: the weight (and bias) gradient of y = conv(x, w) + b, ks in {1, 3}, stride 1, pad ks / 2,
+ * Cin % 16 == 0, any Cout -- a general convolution weight gradient, not a special of the heads.
+ *   x: NHWC view [N,H,W,Cin] (pitch ldx); gy: NHWC view [N,H,W,Cout] (pitch ldgy), the gradient of y;
+ *   gw: OIHW [Cout,Cin,ks,ks], the layout of nn.Conv2d.weight; gb: [Cout] or NULL (not computed).
+ *   The contraction over K = N*H*W pixels runs on the fp32 MFMA in K slabs whose partial sums go to `workspace`
+ *   (ct_conv2d_backward_weight_workspace_bytes(d) bytes; 0 for a rejected descriptor); a second launch adds the slabs in
+ *   slab order.  Both views must stay below 2 GiB (N*H*W*ld*4): the kernel addresses a view through one buffer descriptor. */
+typedef struct ct_conv_bwd_weight_desc {
+    const float *x; int N, H, W, Cin, ldx;
+    const float *gy; int Cout, ldgy;
+    int ks, stride;                             /* stride must be 1 */
+    float *gw; float *gb;
+    float *workspace; size_t workspace_bytes;
+} ct_conv_bwd_weight_desc;
+int ct_conv2d_backward_weight(const ct_conv_bwd_weight_desc *d, void *stream);
+size_t ct_conv2d_backward_weight_workspace_bytes(const ct_conv_bwd_weight_desc *d);
+/* ct_heads_tail_backward: for nheads <= CT_LOSS_MAX_HEADS heads of any width c over one hidden map,
+ *   gmid[p, i*hc + k] = mid[p, i*hc + k] > 0 ? sum_c w2[i][c][k] * gout[i][c][p] : 0     (CT_HEADS_BWD_HIDDEN)
+ *   gw2[i][c][k] = sum_p gout[i][c][p] * mid[p, i*hc + k],  gb2[i][c] = sum_p gout[i][c][p]   (CT_HEADS_BWD_WEIGHT)
+ *   gout: the head's logit gradient, NCHW [N,c,H,W] contiguous -- what ct_generic_loss_backward writes into
+ *   ct_loss_head.grad; w2: [c,hc] = the 1x1 weight; mid: the hidden map AFTER the ReLU, NHWC view [N,H,W,nheads*hc] (pitch
+ *   ldmid); gmid: NHWC view of the same shape (pitch ldgmid, which may differ; channels beyond nheads*hc are not
+ *   written).  The ReLU convention is torch's: gradient 0 where the hidden value is exactly 0.
+ *   flags select what is computed; buffers of the other part may be NULL and are not touched.  With CT_HEADS_BWD_WEIGHT a
+ *   head whose gw2 and gb2 are both NULL is skipped, and either may be NULL on its own.  The sums over the pixels go through
+ *   per-workgroup partials in `workspace` (ct_heads_tail_backward_workspace_bytes(d) bytes; 0 without CT_HEADS_BWD_WEIGHT
+ *   or for a rejected descriptor; it does not depend on which gw2 / gb2 are given) that a second launch adds in a fixed
+ *   order.  Every view is addressed with 64-bit offsets: no 2 GiB limit here, N*H*W < 2^31. */
+#define CT_HEADS_BWD_HIDDEN 1     /* gmid */
+#define CT_HEADS_BWD_WEIGHT 2     /* gw2 / gb2 of the heads that give a buffer */
+typedef struct ct_heads_tail_head {
+    const float *gout; int c;
+    const float *w2;              /* CT_HEADS_BWD_HIDDEN only */
+    float *gw2; float *gb2;       /* CT_HEADS_BWD_WEIGHT only; NULL = not computed */
+} ct_heads_tail_head;
+typedef struct ct_heads_tail_bwd_desc {
+    int N, H, W, hc;
+    const ct_heads_tail_head *heads; int nheads;      /* HOST array */
+    const float *mid; int ldmid;
+    float *gmid; int ldgmid;
+    float *workspace; size_t workspace_bytes;
+    int flags;
+} ct_heads_tail_bwd_desc;
+int ct_heads_tail_backward(const ct_heads_tail_bwd_desc *d, void *stream);
+size_t ct_heads_tail_backward_workspace_bytes(const ct_heads_tail_bwd_desc *d);
 
 /* ---- the three 7x7 stems, fused --------------------------------------------------
  * Replaces DLA.forward's base_layer / pre_img_layer / pre_hm_layer and their sum
