@@ -121,6 +121,33 @@ class HeadsTailBwdDesc(ctypes.Structure):
                 ('flags', ctypes.c_int)]
 
 
+CT_BN_BATCH_STATS = 1
+
+
+class BnDesc(ctypes.Structure):
+    _fields_ = [('z', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('C', ctypes.c_int), ('ldz', ctypes.c_int),
+                ('mean', ctypes.c_void_p), ('var', ctypes.c_void_p), ('invstd', ctypes.c_void_p),
+                ('eps', ctypes.c_float),
+                ('gamma', ctypes.c_void_p), ('beta', ctypes.c_void_p),
+                ('y', ctypes.c_void_p), ('ldy', ctypes.c_int),
+                ('gy', ctypes.c_void_p), ('ldgy', ctypes.c_int),
+                ('gz', ctypes.c_void_p), ('ldgz', ctypes.c_int),
+                ('ggamma', ctypes.c_void_p), ('gbeta', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+                ('flags', ctypes.c_int)]
+
+
+class UpsampleBwdDesc(ctypes.Structure):
+    _fields_ = [('gy', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('C', ctypes.c_int), ('ldgy', ctypes.c_int), ('f', ctypes.c_int),
+                ('w', ctypes.c_void_p),
+                ('gx', ctypes.c_void_p), ('ldgx', ctypes.c_int),
+                ('x', ctypes.c_void_p), ('ldx', ctypes.c_int),
+                ('gw', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
 CT_MAX_FUSED_HEADS = 8
 
 
@@ -229,7 +256,8 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_dcn_v2_backward', 'ct_dcn_v2_backward_workspace_bytes', 'ct_packed_dcn_weight_t_elems', 'ct_pack_dcn_weight_t',
            'ct_generic_loss_forward', 'ct_generic_loss_backward', 'ct_generic_loss_workspace_bytes',
            'ct_conv2d_backward_weight', 'ct_conv2d_backward_weight_workspace_bytes', 'ct_heads_tail_backward',
-           'ct_heads_tail_backward_workspace_bytes', 'ct_stem_forward',
+           'ct_heads_tail_backward_workspace_bytes', 'ct_bn_stats', 'ct_bn_relu_apply', 'ct_bn_relu_backward', 'ct_bn_workspace_bytes',
+           'ct_upsample_add_backward', 'ct_upsample_add_backward_workspace_bytes', 'ct_dcn_mask_sigmoid_backward', 'ct_stem_forward',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
            'ct_decode_pose', 'ct_render_pre_hm',
@@ -305,6 +333,15 @@ def load():
     lib.ct_heads_tail_backward.argtypes = [ctypes.POINTER(HeadsTailBwdDesc), p]
     lib.ct_heads_tail_backward_workspace_bytes.restype = sz
     lib.ct_heads_tail_backward_workspace_bytes.argtypes = [ctypes.POINTER(HeadsTailBwdDesc)]
+    lib.ct_bn_stats.argtypes = [ctypes.POINTER(BnDesc), p]
+    lib.ct_bn_relu_apply.argtypes = [ctypes.POINTER(BnDesc), p]
+    lib.ct_bn_relu_backward.argtypes = [ctypes.POINTER(BnDesc), p]
+    lib.ct_bn_workspace_bytes.restype = sz
+    lib.ct_bn_workspace_bytes.argtypes = [ctypes.POINTER(BnDesc)]
+    lib.ct_upsample_add_backward.argtypes = [ctypes.POINTER(UpsampleBwdDesc), p]
+    lib.ct_upsample_add_backward_workspace_bytes.restype = sz
+    lib.ct_upsample_add_backward_workspace_bytes.argtypes = [ctypes.POINTER(UpsampleBwdDesc)]
+    lib.ct_dcn_mask_sigmoid_backward.argtypes = [p, i, p, i, i, i, i, p]
     lib.ct_stem_forward.argtypes = [p, p, p, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_stem_forward_parts.argtypes = [p, p, p, p, i, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_maxpool2x2.argtypes = [p, i, i, i, i, i, p, i, p]

@@ -230,12 +230,13 @@ def make_dcn_bwd_desc(x, om, gy, wT=None, gx=None, gom=None, gw=None, gb=None, w
     return d
 
 
-def dcn_v2_backward(x, om, gy, wT=None, need_x=True, need_om=True, need_w=True, need_b=True):
+def dcn_v2_backward(x, om, gy, wT=None, need_x=True, need_om=True, need_w=True, need_b=True, gom=None):
     """Gradients of ``dcn_v2(x, om, w) + bias`` for the incoming gradient ``gy`` (NHWC views; ``om`` = the forward's
     offset/mask map, mask after the sigmoid; ``wT`` = pack_weight_t(w), needed for ``need_x`` / ``need_om``).
     Returns ``(gx view, gom view [N,H,W,27 of 32], gw OIHW, gb)``, None for what was not asked for -- no buffer is
     allocated and no kernel runs for those.  ``gx`` is summed with float atomics (equal from run to run only to fp32
-    rounding); the other three are bitwise reproducible."""
+    rounding); the other three are bitwise reproducible.  ``gom``: a caller-owned 27-of-32 view for the offset/mask gradient
+    (the trainable DeformConv passes a zeroed buffer: its five pad channels feed a 32-channel convolution)."""
     lib = _lib.load()
     dev = x.buf.device
     if not (need_x or need_om or need_w or need_b):
@@ -243,7 +244,10 @@ def dcn_v2_backward(x, om, gy, wT=None, need_x=True, need_om=True, need_w=True, 
     if (need_x or need_om) and wT is None:
         raise _lib.CTError('dcn_v2_backward: the input / offset / mask gradients need the transposed weight packing')
     gx = new_view(x.N, x.H, x.W, x.C, dev) if need_x else None
-    gom = View(torch.empty((x.N, x.H, x.W, 32), dtype=torch.float32, device=dev), 0, 27) if need_om else None
+    if not need_om:
+        gom = None
+    elif gom is None:
+        gom = View(torch.empty((x.N, x.H, x.W, 32), dtype=torch.float32, device=dev), 0, 27)
     gw = torch.empty((gy.C, x.C, 3, 3), dtype=torch.float32, device=dev) if need_w or need_b else None
     gb = torch.empty(gy.C, dtype=torch.float32, device=dev) if need_b else None
     d = make_dcn_bwd_desc(x, om, gy, wT, gx, gom, gw, gb)
@@ -508,6 +512,118 @@ def upsample_add(x, w, f, skip, out=None):
     _lib.check(_lib.load().ct_upsample_add(x.ptr, x.N, x.H, x.W, x.C, x.ld, w.data_ptr(), f, skip.ptr, skip.ld,
                                            out.ptr, out.ld, _lib.stream_ptr()), 'ct_upsample_add')
     return out
+
+
+def _bn_desc(z, mean=None, invstd=None, gamma=None, beta=None):
+    d = _lib.BnDesc()
+    d.z, d.N, d.H, d.W, d.C, d.ldz = z.ptr, z.N, z.H, z.W, z.C, z.ld
+    d.mean, d.invstd, d.gamma, d.beta = _p(mean), _p(invstd), _p(gamma), _p(beta)
+    return d
+
+
+def _bn_workspace(lib, d, dev):
+    need = lib.ct_bn_workspace_bytes(ctypes.byref(d))
+    if not need:
+        raise _lib.CTError('ct_bn_workspace_bytes: %s' % lib.ct_last_error().decode())
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    return ws
+
+
+def _bn_vec(t, C, what):
+    if t.numel() != C or t.dtype != torch.float32 or not t.is_contiguous() or t.device != what.buf.device:
+        raise _lib.CTError('batch norm: a per-channel vector must be contiguous fp32 [%d] on %s' % (C, what.buf.device))
+    return t
+
+
+def bn_stats(z, eps=1e-5):
+    """Per-channel (mean, biased variance, 1 / sqrt(var + eps)) of the NHWC view ``z`` over N*H*W: two passes (sum, then squared
+    deviations), four launches, bitwise reproducible."""
+    lib = _lib.load()
+    dev = z.buf.device
+    mean, var, invstd = (torch.empty(z.C, dtype=torch.float32, device=dev) for _ in range(3))
+    d = _bn_desc(z, mean, invstd)
+    d.var, d.eps = var.data_ptr(), eps
+    _ws = _bn_workspace(lib, d, dev)
+    _lib.check(lib.ct_bn_stats(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_stats')
+    return mean, var, invstd
+
+
+def bn_relu_apply(z, mean, invstd, gamma, beta, out=None):
+    """y = max(0, fma(z, a, b)), a = gamma * invstd, b = fma(-mean, a, beta) on NHWC views; allocates ``out`` if not given."""
+    lib = _lib.load()
+    if out is None:
+        out = new_view(z.N, z.H, z.W, z.C, z.buf.device)
+    d = _bn_desc(z, *(_bn_vec(t, z.C, z) for t in (mean, invstd, gamma, beta)))
+    d.y, d.ldy = out.ptr, out.ld
+    _lib.check(lib.ct_bn_relu_apply(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_relu_apply')
+    return out
+
+
+def bn_relu_backward(z, gy, mean, invstd, gamma, beta, batch_stats, need_z=True, need_gamma=True, need_beta=True):
+    """Gradients of ``bn_relu_apply`` (with ``batch_stats``: through the batch statistics as well) for the output gradient
+    ``gy`` -> ``(gz view, ggamma, gbeta)``, None for what was not asked for.  Bitwise reproducible."""
+    lib = _lib.load()
+    dev = z.buf.device
+    if not (need_z or need_gamma or need_beta):
+        return None, None, None
+    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
+        raise _lib.CTError('bn_relu_backward: gy does not have the shape of z')
+    d = _bn_desc(z, *(_bn_vec(t, z.C, z) for t in (mean, invstd, gamma, beta)))
+    d.gy, d.ldgy = gy.ptr, gy.ld
+    gz = new_view(z.N, z.H, z.W, z.C, dev) if need_z else None
+    gg = torch.empty(z.C, dtype=torch.float32, device=dev) if need_gamma else None
+    gb = torch.empty(z.C, dtype=torch.float32, device=dev) if need_beta else None
+    if gz is not None:
+        d.gz, d.ldgz = gz.ptr, gz.ld
+    d.ggamma, d.gbeta = _p(gg), _p(gb)
+    d.flags = _lib.CT_BN_BATCH_STATS if batch_stats else 0
+    if need_gamma or need_beta or batch_stats:
+        _ws = _bn_workspace(lib, d, dev)
+    _lib.check(lib.ct_bn_relu_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_relu_backward')
+    return gz, gg, gb
+
+
+def upsample_add_backward(x, w, f, gy, need_x=True, need_w=True):
+    """Gradients of ``upsample_add(x, w, f, skip)`` for the output gradient ``gy`` (NHWC views; ``w``: the module weight
+    [C,1,2f,2f] or an ``upsample_weight`` result; ``x`` may be None without ``need_w``) -> ``(gx view, gw [C,1,2f,2f], gskip)``,
+    None for what was not asked for.  ``gskip`` is ``gy`` itself: no kernel and no copy.  Bitwise reproducible."""
+    lib = _lib.load()
+    dev = gy.buf.device
+    H, W = gy.H // f, gy.W // f
+    if f not in (2, 4, 8) or (H * f, W * f) != (gy.H, gy.W) or (need_w and (x.N, x.H, x.W, x.C) != (gy.N, H, W, gy.C)):
+        raise _lib.CTError('upsample_add_backward: f=%s, gy %s, x %s do not fit' % (
+            f, (gy.N, gy.H, gy.W, gy.C), None if x is None else (x.N, x.H, x.W, x.C)))
+    if not (need_x or need_w):
+        return None, None, gy
+    d = _lib.UpsampleBwdDesc()
+    d.gy, d.N, d.H, d.W, d.C, d.ldgy, d.f = gy.ptr, gy.N, H, W, gy.C, gy.ld, f
+    gx = gw = None
+    if need_x:
+        if w.dim() == 4:
+            w = upsample_weight(w)
+        gx = new_view(gy.N, H, W, gy.C, dev)
+        d.w, d.gx, d.ldgx = w.data_ptr(), gx.ptr, gx.ld
+    if need_w:
+        gw = torch.empty((gy.C, 1, 2 * f, 2 * f), dtype=torch.float32, device=dev)
+        d.x, d.ldx, d.gw = x.ptr, x.ld, gw.data_ptr()
+        need = lib.ct_upsample_add_backward_workspace_bytes(ctypes.byref(d))
+        if not need:
+            raise _lib.CTError('ct_upsample_add_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
+        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    _lib.check(lib.ct_upsample_add_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_upsample_add_backward')
+    return gx, gw, gy
+
+
+def mask_sigmoid_backward(gom, om):
+    """g <- g * m * (1 - m) on the nine mask channels (18..26) of the offset/mask gradient ``gom``, in place; ``om`` = the
+    forward's offset/mask map (mask after the sigmoid)."""
+    if (gom.N, gom.H, gom.W) != (om.N, om.H, om.W) or gom.C < 27 or om.C < 27:
+        raise _lib.CTError('mask_sigmoid_backward: two 27-channel views of one shape expected')
+    _lib.check(_lib.load().ct_dcn_mask_sigmoid_backward(gom.ptr, gom.ld, om.ptr, om.ld, om.N, om.H, om.W, _lib.stream_ptr()),
+               'ct_dcn_mask_sigmoid_backward')
+    return gom
 
 
 # field order of a packed decode row after (score, cls, xs0, ys0)

@@ -356,6 +356,57 @@ typedef struct ct_heads_tail_bwd_desc {
 int ct_heads_tail_backward(const ct_heads_tail_bwd_desc *d, void *stream);
 size_t ct_heads_tail_backward_workspace_bytes(const ct_heads_tail_bwd_desc *d);
 
+/* ---- the trainable neck (DeformConv / IDAUp / DLAUp, dla.py:506-574); additions under ABI 103.  All fp32 on NHWC views with
+ * a channel pitch (ld >= C, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, channel slices allowed).  No atomics: every sum
+ * runs thread -> workgroup -> slab in a fixed order, slab counts depend on the shapes only, every result is bitwise equal from
+ * run to run.  A view stays below 2 GiB (N*H*W*ld*4): the kernels address it with 32-bit offsets.
+ *
+ * ct_bn_desc serves three calls over one pre-activation map z [N,H,W,C]:
+ *   ct_bn_stats:          mean[c], var[c] (biased, two passes: sum of z - z[pixel 0], then sum of squared deviations), invstd[c] = 1/sqrt(var + eps)
+ *   ct_bn_relu_apply:     y = max(0, fma(z, a, b)), a = gamma * invstd, b = fma(-mean, a, beta)
+ *   ct_bn_relu_backward:  g = gy where the recomputed pre-activation is > 0, else 0 (torch's ReLU: 0 at exactly 0);
+ *                         gbeta = sum g, ggamma = sum g * xhat, xhat = (z - mean) * invstd;
+ *                         gz = a * (g - mean(g) - xhat * mean(g * xhat)) with CT_BN_BATCH_STATS, a * g without
+ *   mean / invstd are what the forward used (batch or running statistics).  gz, ggamma, gbeta may each be NULL (not computed;
+ *   a frozen gamma / beta still gives the batch-statistics gz).  ct_bn_stats and ct_bn_relu_backward need
+ *   ct_bn_workspace_bytes(d) bytes of workspace (0 for a rejected descriptor); ct_bn_relu_apply needs none. */
+#define CT_BN_BATCH_STATS 1
+typedef struct ct_bn_desc {
+    const float *z; int N, H, W, C, ldz;
+    float *mean; float *var; float *invstd;     /* [C] each; var: ct_bn_stats only */
+    float eps;                                  /* ct_bn_stats only */
+    const float *gamma; const float *beta;      /* [C] */
+    float *y; int ldy;                          /* ct_bn_relu_apply */
+    const float *gy; int ldgy;                  /* ct_bn_relu_backward */
+    float *gz; int ldgz;
+    float *ggamma; float *gbeta;
+    float *workspace; size_t workspace_bytes;
+    int flags;
+} ct_bn_desc;
+int ct_bn_stats(const ct_bn_desc *d, void *stream);
+int ct_bn_relu_apply(const ct_bn_desc *d, void *stream);
+int ct_bn_relu_backward(const ct_bn_desc *d, void *stream);
+size_t ct_bn_workspace_bytes(const ct_bn_desc *d);
+/* ct_upsample_add_backward: the backward of ct_upsample_add for the output gradient gy [N,fH,fW,C] (H, W = the INPUT grid):
+ *   gx[n,iy,ix,c] = sum_{ky,kx < 2f} gy[n, iy*f - f/2 + ky, ix*f - f/2 + kx, c] * w[ky,kx,c]     (w: ct_upsample_add's [2f,2f,C])
+ *   gw[c,ky,kx]   = sum_{n,iy,ix} x[n,iy,ix,c] * gy[same index]            (gw: the module's [C,1,2f,2f] layout)
+ *   gx / gw may be NULL (not computed; w is needed for gx, x for gw).  The gradient of the skip input is gy itself.  gw goes
+ *   through per-slab partials in `workspace` (ct_upsample_add_backward_workspace_bytes(d) bytes; 0 for a rejected descriptor). */
+typedef struct ct_upsample_bwd_desc {
+    const float *gy; int N, H, W, C, ldgy;
+    int f;
+    const float *w;
+    float *gx; int ldgx;
+    const float *x; int ldx;
+    float *gw;
+    float *workspace; size_t workspace_bytes;
+} ct_upsample_bwd_desc;
+int ct_upsample_add_backward(const ct_upsample_bwd_desc *d, void *stream);
+size_t ct_upsample_add_backward_workspace_bytes(const ct_upsample_bwd_desc *d);
+/* g[p, 18 + j] *= m * (1 - m), m = om[p, 18 + j], j < 9: the sigmoid of the DCN mask channels, in place on the offset/mask
+ * gradient of ct_dcn_v2_backward (om = the forward's map, mask after the sigmoid) */
+int ct_dcn_mask_sigmoid_backward(float *g, int ldg, const float *om, int ldom, int N, int H, int W, void *stream);
+
 /* ---- the three 7x7 stems, fused --------------------------------------------------
  * Replaces DLA.forward's base_layer / pre_img_layer / pre_hm_layer and their sum
  * (dla.py:238-267,305-311): y = sum_s relu(bn_s(conv7x7_s(in_s))), inputs NCHW
