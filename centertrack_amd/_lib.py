@@ -148,6 +148,25 @@ class UpsampleBwdDesc(ctypes.Structure):
                 ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
 
 
+CT_BN_ACT_RELU = 2
+
+
+class ConvS2BwdDesc(ctypes.Structure):
+    _fields_ = [('x', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('Cin', ctypes.c_int), ('ldx', ctypes.c_int),
+                ('gy', ctypes.c_void_p), ('Cout', ctypes.c_int), ('ldgy', ctypes.c_int),
+                ('w_s2t', ctypes.c_void_p),
+                ('gx', ctypes.c_void_p), ('ldgx', ctypes.c_int),
+                ('gw', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+                ('flags', ctypes.c_int)]
+
+
+class BnActDesc(ctypes.Structure):
+    _fields_ = BnDesc._fields_ + [('res', ctypes.c_void_p), ('ldr', ctypes.c_int),
+                                  ('gres', ctypes.c_void_p), ('ldgres', ctypes.c_int)]
+
+
 CT_MAX_FUSED_HEADS = 8
 
 
@@ -257,7 +276,9 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_generic_loss_forward', 'ct_generic_loss_backward', 'ct_generic_loss_workspace_bytes',
            'ct_conv2d_backward_weight', 'ct_conv2d_backward_weight_workspace_bytes', 'ct_heads_tail_backward',
            'ct_heads_tail_backward_workspace_bytes', 'ct_bn_stats', 'ct_bn_relu_apply', 'ct_bn_relu_backward', 'ct_bn_workspace_bytes',
-           'ct_upsample_add_backward', 'ct_upsample_add_backward_workspace_bytes', 'ct_dcn_mask_sigmoid_backward', 'ct_stem_forward',
+           'ct_upsample_add_backward', 'ct_upsample_add_backward_workspace_bytes', 'ct_dcn_mask_sigmoid_backward',
+           'ct_conv2d_s2_backward', 'ct_conv2d_s2_backward_workspace_bytes', 'ct_packed_conv_weight_s2t_elems', 'ct_pack_conv_weight_s2t',
+           'ct_bn_act_apply', 'ct_bn_act_backward', 'ct_bn_act_workspace_bytes', 'ct_maxpool2x2_backward', 'ct_stem_forward',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
            'ct_decode_pose', 'ct_render_pre_hm',
@@ -342,6 +363,17 @@ def load():
     lib.ct_upsample_add_backward_workspace_bytes.restype = sz
     lib.ct_upsample_add_backward_workspace_bytes.argtypes = [ctypes.POINTER(UpsampleBwdDesc)]
     lib.ct_dcn_mask_sigmoid_backward.argtypes = [p, i, p, i, i, i, i, p]
+    lib.ct_conv2d_s2_backward.argtypes = [ctypes.POINTER(ConvS2BwdDesc), p]
+    lib.ct_conv2d_s2_backward_workspace_bytes.restype = sz
+    lib.ct_conv2d_s2_backward_workspace_bytes.argtypes = [ctypes.POINTER(ConvS2BwdDesc)]
+    lib.ct_packed_conv_weight_s2t_elems.restype = sz
+    lib.ct_packed_conv_weight_s2t_elems.argtypes = [i, i]
+    lib.ct_pack_conv_weight_s2t.argtypes = [p, p, i, i, p]
+    lib.ct_bn_act_apply.argtypes = [ctypes.POINTER(BnActDesc), p]
+    lib.ct_bn_act_backward.argtypes = [ctypes.POINTER(BnActDesc), p]
+    lib.ct_bn_act_workspace_bytes.restype = sz
+    lib.ct_bn_act_workspace_bytes.argtypes = [ctypes.POINTER(BnActDesc)]
+    lib.ct_maxpool2x2_backward.argtypes = [p, i, i, i, i, i, p, i, p, i, p, i, p]
     lib.ct_stem_forward.argtypes = [p, p, p, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_stem_forward_parts.argtypes = [p, p, p, p, i, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_maxpool2x2.argtypes = [p, i, i, i, i, i, p, i, p]

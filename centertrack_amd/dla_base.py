@@ -1,0 +1,406 @@
+"""The DLA-34 backbone base as trainable drop-in modules: ``BasicBlock``, ``Root``, ``Tree``, ``DLA`` and ``dla34`` of the
+reference's ``model/networks/dla.py`` (lines 38-66, 154-316, 333-342), with its constructor signatures, state-dict keys,
+buffer names, default initialisation and calling conventions, on the kernels of libcentertrack_hip.so (DESIGN.md section 13,
+INTEGRATION.md section A).
+
+Behind the stems every tensor is an NHWC ``[N,H,W,C]`` fp32 tensor; NCHW <-> NHWC conversion happens once per input and once
+per returned tensor of the outermost module that is called, and every module also has ``forward_nhwc``.  The unit of the
+backbone and of autograd is ``conv (ks 1 | 3, stride 1 | 2, no bias) -> BatchNorm (-> + residual) (-> ReLU)``: ``ct_conv2d``
+(the raw ``z``), ``ct_bn_stats`` (training mode only) and ``ct_bn_act_apply``; its backward is ``ct_bn_act_backward``, then
+the weight gradient (``ct_conv2d_backward_weight`` / ``ct_conv2d_s2_backward``) and the input gradient (``ct_conv2d`` with the
+transposed, flipped weight / ``ct_conv2d_s2_backward``).  ``Tree.downsample`` is ``ct_maxpool2x2``; where a ``Tree`` feeds one
+tensor to a stride-2 block and to the pool, the block's first unit returns the pooled map as a second output and its backward
+hands the conv's input gradient to ``ct_maxpool2x2_backward`` as ``add``.
+
+The parameters live in real ``nn.Conv2d`` / ``nn.BatchNorm2d`` objects (``load_state_dict``, optimizers and torch's default
+initialisation work unchanged) and are packed at every call: no packing is cached.  Statistics follow torch: batch statistics
+when, and only when, the BatchNorm is in training mode, and then the running statistics are updated as torch does.  A graph is
+recorded only under ``dcn_v2.trainable()`` with autograd enabled; otherwise the same forward runs with nothing saved and
+returns the same bits.  CUDA fp32 tensors only: there is no CPU fallback.
+
+Not covered: the three 7x7 stems (``base_layer``, ``pre_img_layer``, ``pre_hm_layer``) are ``nn.Sequential`` modules that
+torch runs (NCHW; their sum is converted once); ``Bottleneck`` / ``BottleneckX``; dilation; nothing is ever downloaded."""
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib, ops
+from .dla_up import BN_MOMENTUM, _recording, _ToNCHW, _ToNHWC, update_running_stats
+from .ops import View
+
+# None = off; a list receives, in call order, the NHWC output of every conv-BN-act unit, of every pool and (as NHWC views of
+# the NCHW maps) of every stem: what a float64 truth needs to take the ReLU masks and pool selections of this forward
+trace = None
+
+
+def _emit(t):
+    if trace is not None:
+        trace.append(t.detach())
+
+
+def _need_cuda(x, what='backbone'):
+    if not x.is_cuda:
+        raise _lib.CTError('centertrack_amd %s runs on an MI355X only (got a %s tensor); no CPU fallback' % (what, x.device))
+    if x.dtype != torch.float32:
+        raise _lib.CTError('centertrack_amd %s computes in fp32 (got %s)' % (what, x.dtype))
+    if x.dim() != 4:
+        raise _lib.CTError('centertrack_amd %s wants a 4-d tensor (got %s)' % (what, tuple(x.shape)))
+
+
+def to_nhwc(x):
+    """NCHW fp32 CUDA tensor -> contiguous ``[N,H,W,C]`` tensor (differentiable while a graph is recorded)"""
+    _need_cuda(x)
+    if x.shape[1] % 4:
+        raise _lib.CTError('centertrack_amd backbone needs channels %% 4 == 0 (got %d)' % x.shape[1])
+    if _recording():
+        return _ToNHWC.apply(x)
+    with torch.no_grad():
+        return ops.view_from_nchw(x).buf
+
+
+def to_nchw(x):
+    if _recording():
+        return _ToNCHW.apply(x)
+    with torch.no_grad():
+        return ops.view_to_nchw(View(x))
+
+
+def _check_channels(*cs):
+    for c in cs:
+        if c <= 0 or c % 16:
+            raise _lib.CTError('centertrack_amd backbone needs channel counts that are multiples of 16 (got %d)' % c)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# conv -> BatchNorm (-> + residual) (-> ReLU)
+
+def _unit_forward(x, conv, bn, res, relu, pool):
+    """The unit on the NHWC view ``x`` -> (output view, pooled view of ``x`` or None, what a backward needs)"""
+    ks, stride = conv.kernel_size[0], conv.stride[0]
+    if x.C != conv.in_channels:
+        raise _lib.CTError('Conv2d(%d, %d) of the backbone got %d channels' % (conv.in_channels, conv.out_channels, x.C))
+    if stride == 2 and (x.H % 2 or x.W % 2):
+        raise _lib.CTError('centertrack_amd backbone: a stride-2 level needs even H and W (got %d x %d)' % (x.H, x.W))
+    z = ops.conv2d(x, ops.pack_weight(conv.weight.detach()), conv.out_channels, ks, stride)
+    pooled = ops.maxpool2x2(x) if pool else None
+    batch = bn.training or bn.running_mean is None
+    if batch:
+        P = z.N * z.H * z.W
+        if P == 1:
+            raise _lib.CTError('backbone: training-mode BatchNorm needs more than one value per channel (N*H*W == 1)')
+        mean, var, invstd = ops.bn_stats(z, bn.eps)
+        if bn.training and bn.running_mean is not None:
+            update_running_stats(bn, mean, var, P)
+    else:
+        mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+    y = ops.bn_act_apply(z, mean, invstd, bn.weight.detach(), bn.bias.detach(), res=res, relu=relu)
+    return y, pooled, (z, mean, invstd, batch)
+
+
+class _ConvBnActFunction(torch.autograd.Function):
+    """One unit over ``[N,H,W,C]`` tensors -> ``y`` or, with ``pool``, ``(y, max_pool2d(x, 2, 2))``.  Saved: the input, the raw
+    convolution output ``z``, the statistics and the residual; the ReLU mask is recomputed from them with the forward's own
+    arithmetic, the pool selection from the input."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, res, conv, bn, relu, pool):
+        y, pooled, (z, mean, invstd, batch) = _unit_forward(View(x), conv, bn, None if res is None else View(res), relu, pool)
+        # z, mean and invstd are kept on ctx, not through save_for_backward: they are private to this call (z and the batch
+        # statistics are allocated here, running statistics are cloned), nobody else holds them, so there is no in-place write
+        # for autograd's version check to catch
+        ctx.z, ctx.mean, ctx.invstd, ctx.batch = z, mean if batch else mean.clone(), invstd, batch
+        ctx.relu, ctx.pool, ctx.ks, ctx.stride = relu, pool, conv.kernel_size[0], conv.stride[0]
+        ctx.save_for_backward(x, weight, gamma, beta, res)
+        ctx.set_materialize_grads(False)
+        return (y.buf, pooled.buf) if pool else y.buf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, gpool=None):
+        x, weight, gamma, beta, res = ctx.saved_tensors
+        need_x, need_w, need_gamma, need_beta, need_res = ctx.needs_input_grad[:5]
+        need_res = need_res and res is not None
+        xv = View(x)
+        gx = gw = gg = gb = gres = None
+        if gy is not None:
+            gy = gy.contiguous()
+            need_z = need_x or need_w
+            # without the ReLU the residual's gradient is the incoming tensor itself: no kernel, no copy
+            gz, gr, gg, gb = ops.bn_act_backward(ctx.z, View(gy), ctx.mean, ctx.invstd, gamma.detach(), beta.detach(), ctx.batch,
+                                                 res=None if res is None else View(res), relu=ctx.relu, need_z=need_z,
+                                                 need_res=need_res and ctx.relu, need_gamma=need_gamma, need_beta=need_beta)
+            if need_res:
+                gres = gr.buf if ctx.relu else gy
+            if ctx.stride == 2:
+                gx, gw = ops.conv_s2_backward(xv, gz, weight.detach(), need_x=need_x, need_w=need_w) if need_z else (None, None)
+            else:
+                if need_w:
+                    gw, _ = ops.conv_backward_weight(xv, gz, ctx.ks, need_bias=False)
+                if need_x:
+                    # conv(gz, w^T): wT[ci, co, ky, kx] = w[co, ci, ks - 1 - ky, ks - 1 - kx], on the forward conv kernels
+                    wt = weight.detach().permute(1, 0, 2, 3).flip(2, 3).contiguous()
+                    gx = ops.conv2d(gz, ops.pack_weight(wt), xv.C, ctx.ks, 1)
+        if ctx.pool and gpool is not None and need_x:
+            gx = ops.maxpool2x2_backward(xv, View(gpool.contiguous()), add=gx)
+        return (gx.buf if gx is not None else None, gw, gg, gb, gres, None, None, None, None)
+
+
+class _MaxPoolFunction(torch.autograd.Function):
+    """``max_pool2d(x, 2, 2)`` over ``[N,H,W,C]`` tensors on its own (a ``Tree`` whose first child is a ``Tree``)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.maxpool2x2(View(x)).buf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        return ops.maxpool2x2_backward(View(x), View(gy.contiguous())).buf
+
+
+def _conv_bn_act(x, conv, bn, res=None, relu=True, pool=False):
+    """The unit on ``[N,H,W,C]`` tensors; with ``pool`` -> (y, the 2x2 max-pool of ``x``)"""
+    x = x.contiguous()
+    res = None if res is None else res.contiguous()
+    if _recording():
+        out = _ConvBnActFunction.apply(x, conv.weight, bn.weight, bn.bias, res, conv, bn, relu, pool)
+    else:
+        with torch.no_grad():
+            y, pooled, _ = _unit_forward(View(x), conv, bn, None if res is None else View(res), relu, pool)
+            out = (y.buf, pooled.buf) if pool else y.buf
+    for t in (out if pool else (out,)):
+        _emit(t)
+    return out
+
+
+def _maxpool(x):
+    x = x.contiguous()
+    if x.shape[1] % 2 or x.shape[2] % 2:
+        raise _lib.CTError('centertrack_amd backbone: the 2x2 max-pool needs even H and W (got %d x %d)' % (x.shape[1], x.shape[2]))
+    if _recording():
+        y = _MaxPoolFunction.apply(x)
+    else:
+        with torch.no_grad():
+            y = ops.maxpool2x2(View(x)).buf
+    _emit(y)
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the modules
+
+def _no_dilation(dilation):
+    if dilation != 1:
+        raise _lib.CTError('centertrack_amd backbone supports dilation 1 only (got %s)' % (dilation,))
+
+
+class BasicBlock(nn.Module):
+    """Reference ``BasicBlock(inplanes, planes, stride=1, dilation=1)``"""
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1):
+        super().__init__()
+        _no_dilation(dilation)
+        if stride not in (1, 2):
+            raise _lib.CTError('centertrack_amd BasicBlock supports stride 1 and 2 (got %s)' % (stride,))
+        _check_channels(inplanes, planes)
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=dilation, bias=False, dilation=dilation)
+        self.bn1 = nn.BatchNorm2d(planes, momentum=BN_MOMENTUM)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=dilation, bias=False, dilation=dilation)
+        self.bn2 = nn.BatchNorm2d(planes, momentum=BN_MOMENTUM)
+        self.stride = stride
+
+    def first_half(self, x, pool=False):
+        return _conv_bn_act(x, self.conv1, self.bn1, relu=True, pool=pool)
+
+    def second_half(self, h, residual):
+        return _conv_bn_act(h, self.conv2, self.bn2, res=residual, relu=True)
+
+    def forward_nhwc(self, x, residual=None):
+        return self.second_half(self.first_half(x), x if residual is None else residual)
+
+    def forward(self, x, residual=None):
+        return to_nchw(self.forward_nhwc(to_nhwc(x), None if residual is None else to_nhwc(residual)))
+
+
+class Root(nn.Module):
+    """Reference ``Root(in_channels, out_channels, kernel_size, residual)``; ``forward(*x)`` concatenates its arguments"""
+
+    def __init__(self, in_channels, out_channels, kernel_size, residual):
+        super().__init__()
+        if kernel_size != 1:
+            raise _lib.CTError('centertrack_amd Root supports root_kernel_size 1 only (got %s)' % (kernel_size,))
+        _check_channels(in_channels, out_channels)
+        self.conv = nn.Conv2d(in_channels, out_channels, 1, stride=1, bias=False, padding=(kernel_size - 1) // 2)
+        self.bn = nn.BatchNorm2d(out_channels, momentum=BN_MOMENTUM)
+        self.relu = nn.ReLU(inplace=True)
+        self.residual = residual
+
+    def forward_nhwc(self, *x):
+        return _conv_bn_act(torch.cat(x, 3), self.conv, self.bn, res=x[0] if self.residual else None, relu=True)
+
+    def forward(self, *x):
+        return to_nchw(self.forward_nhwc(*[to_nhwc(t) for t in x]))
+
+
+class Tree(nn.Module):
+    """Reference ``Tree(levels, block, in_channels, out_channels, stride=1, level_root=False, root_dim=0, root_kernel_size=1,
+    dilation=1, root_residual=False)``.  As in the reference, the ``residual`` argument of ``forward`` is overwritten by the
+    tree's own (``project(downsample(x))``), and a ``project`` whose result no block reads still runs."""
+
+    def __init__(self, levels, block, in_channels, out_channels, stride=1, level_root=False, root_dim=0, root_kernel_size=1,
+                 dilation=1, root_residual=False):
+        super().__init__()
+        if block is not BasicBlock:
+            raise _lib.CTError('centertrack_amd Tree builds its blocks from centertrack_amd.dla_base.BasicBlock only')
+        _no_dilation(dilation)
+        if stride not in (1, 2):
+            raise _lib.CTError('centertrack_amd Tree supports stride 1 and 2 (got %s)' % (stride,))
+        if root_dim == 0:
+            root_dim = 2 * out_channels
+        if level_root:
+            root_dim += in_channels
+        if levels == 1:
+            self.tree1 = block(in_channels, out_channels, stride, dilation=dilation)
+            self.tree2 = block(out_channels, out_channels, 1, dilation=dilation)
+        else:
+            self.tree1 = Tree(levels - 1, block, in_channels, out_channels, stride, root_dim=0,
+                              root_kernel_size=root_kernel_size, dilation=dilation, root_residual=root_residual)
+            self.tree2 = Tree(levels - 1, block, out_channels, out_channels, root_dim=root_dim + out_channels,
+                              root_kernel_size=root_kernel_size, dilation=dilation, root_residual=root_residual)
+        if levels == 1:
+            self.root = Root(root_dim, out_channels, root_kernel_size, root_residual)
+        self.level_root = level_root
+        self.root_dim = root_dim
+        self.downsample = None
+        self.project = None
+        self.levels = levels
+        if stride > 1:
+            self.downsample = nn.MaxPool2d(stride, stride=stride)
+        if in_channels != out_channels:
+            self.project = nn.Sequential(nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, bias=False),
+                                         nn.BatchNorm2d(out_channels, momentum=BN_MOMENTUM))
+
+    def _project(self, bottom):
+        return _conv_bn_act(bottom, self.project[0], self.project[1], relu=False) if self.project else bottom
+
+    def forward_nhwc(self, x, residual=None, children=None):
+        children = [] if children is None else children
+        if self.levels == 1:
+            # the block's first unit and the pool read the same tensor: one autograd node, one input-gradient pass
+            if self.downsample:
+                h, bottom = self.tree1.first_half(x, pool=True)
+            else:
+                h, bottom = self.tree1.first_half(x), x
+            residual = self._project(bottom)
+            if self.level_root:
+                children.append(bottom)
+            x1 = self.tree1.second_half(h, residual)
+            x2 = self.tree2.forward_nhwc(x1)
+            return self.root.forward_nhwc(x2, x1, *children)
+        bottom = _maxpool(x) if self.downsample else x
+        self._project(bottom)                       # the reference computes it (and moves its running statistics); nobody reads it
+        if self.level_root:
+            children.append(bottom)
+        x1 = self.tree1.forward_nhwc(x)
+        children.append(x1)
+        return self.tree2.forward_nhwc(x1, children=children)
+
+    def forward(self, x, residual=None, children=None):
+        children = None if children is None else [to_nhwc(c) for c in children]
+        return to_nchw(self.forward_nhwc(to_nhwc(x), children=children))
+
+
+class DLA(nn.Module):
+    """Reference ``DLA(levels, channels, num_classes=1000, block=BasicBlock, residual_root=False, linear_root=False,
+    opt=None)``.  ``forward(x, pre_img=None, pre_hm=None)`` returns the six level outputs (NCHW), ``forward_nhwc`` the same as
+    ``[N,H,W,C]`` tensors.  The stems are torch modules."""
+
+    def __init__(self, levels, channels, num_classes=1000, block=BasicBlock, residual_root=False, linear_root=False, opt=None):
+        super().__init__()
+        if block is not BasicBlock:
+            raise _lib.CTError('centertrack_amd DLA builds its levels from centertrack_amd.dla_base.BasicBlock only '
+                               '(Bottleneck / BottleneckX are not covered)')
+        _check_channels(*channels)
+        self.channels = channels
+        self.num_classes = num_classes
+
+        def stem(cin):
+            return nn.Sequential(nn.Conv2d(cin, channels[0], kernel_size=7, stride=1, padding=3, bias=False),
+                                 nn.BatchNorm2d(channels[0], momentum=BN_MOMENTUM), nn.ReLU(inplace=True))
+        self.base_layer = stem(3)
+        self.level0 = self._make_conv_level(channels[0], channels[0], levels[0])
+        self.level1 = self._make_conv_level(channels[0], channels[1], levels[1], stride=2)
+        self.level2 = Tree(levels[2], block, channels[1], channels[2], 2, level_root=False, root_residual=residual_root)
+        self.level3 = Tree(levels[3], block, channels[2], channels[3], 2, level_root=True, root_residual=residual_root)
+        self.level4 = Tree(levels[4], block, channels[3], channels[4], 2, level_root=True, root_residual=residual_root)
+        self.level5 = Tree(levels[5], block, channels[4], channels[5], 2, level_root=True, root_residual=residual_root)
+        if getattr(opt, 'pre_img', False):
+            self.pre_img_layer = stem(3)
+        if getattr(opt, 'pre_hm', False):
+            self.pre_hm_layer = stem(1)
+
+    def _make_conv_level(self, inplanes, planes, convs, stride=1, dilation=1):
+        _no_dilation(dilation)
+        modules = []
+        for i in range(convs):
+            modules.extend([nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride if i == 0 else 1, padding=dilation, bias=False,
+                                      dilation=dilation),
+                            nn.BatchNorm2d(planes, momentum=BN_MOMENTUM), nn.ReLU(inplace=True)])
+            inplanes = planes
+        return nn.Sequential(*modules)
+
+    def _stems(self, x, pre_img, pre_hm):
+        parts = [(self.base_layer, x)]
+        for name, t in (('pre_img_layer', pre_img), ('pre_hm_layer', pre_hm)):
+            if t is not None:
+                if not hasattr(self, name):
+                    raise _lib.CTError('DLA: built without %s (opt.%s)' % (name, name[:-len('_layer')]))
+                parts.append((getattr(self, name), t))
+        y = None
+        for layer, t in parts:
+            _need_cuda(t)
+            s = layer(t)
+            _emit(s.permute(0, 2, 3, 1))
+            y = s if y is None else y + s
+        return y
+
+    def forward_nhwc(self, x, pre_img=None, pre_hm=None):
+        """NCHW inputs (the stems are torch's) -> the six level outputs as ``[N,H,W,C]`` tensors"""
+        with torch.set_grad_enabled(_recording()):
+            y = self._stems(x, pre_img, pre_hm)
+        y = to_nhwc(y)
+        out = []
+        for i in range(6):
+            level = getattr(self, 'level{}'.format(i))
+            if isinstance(level, Tree):
+                y = level.forward_nhwc(y)
+            else:
+                for j in range(0, len(level), 3):
+                    y = _conv_bn_act(y, level[j], level[j + 1], relu=True)
+            out.append(y)
+        return out
+
+    def forward(self, x, pre_img=None, pre_hm=None):
+        return [to_nchw(t) for t in self.forward_nhwc(x, pre_img, pre_hm)]
+
+    def load_pretrained_model(self, data='imagenet', name='dla34', hash='ba72cf86'):
+        """The reference's loader for a LOCAL ``.pth`` (``data + name`` is its path); nothing is downloaded"""
+        if not name.endswith('.pth'):
+            raise _lib.CTError('centertrack_amd DLA.load_pretrained_model reads a local .pth only (got name=%r): nothing is '
+                               'downloaded' % (name,))
+        model_weights = torch.load(data + name)
+        num_classes = len(model_weights[list(model_weights.keys())[-1]])
+        self.fc = nn.Conv2d(self.channels[-1], num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        self.load_state_dict(model_weights, strict=False)
+
+
+def dla34(pretrained=True, **kwargs):
+    """Reference ``dla34``; ``pretrained=True`` would download the ImageNet weights and is refused: build with
+    ``pretrained=False`` and call ``load_pretrained_model`` with a local file"""
+    if pretrained:
+        raise _lib.CTError('centertrack_amd dla34(pretrained=True) is refused: nothing is downloaded; use pretrained=False and '
+                           'DLA.load_pretrained_model(data=<directory>, name=<file>.pth)')
+    return DLA([1, 1, 1, 2, 2, 1], [16, 32, 64, 128, 256, 512], block=BasicBlock, **kwargs)

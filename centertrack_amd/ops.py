@@ -626,6 +626,124 @@ def mask_sigmoid_backward(gom, om):
     return gom
 
 
+def pack_weight_s2t(w):
+    """OIHW 3x3 conv weight -> the fragment layout the stride-2 input gradient contracts gy with (centertrack_hip.h)."""
+    lib = _lib.load()
+    w = w.contiguous().float()
+    Cout, Cin, ks, ks2 = w.shape
+    n = lib.ct_packed_conv_weight_s2t_elems(Cout, Cin)
+    if ks != 3 or ks2 != 3 or not n:
+        raise _lib.CTError('pack_weight_s2t: a [Cout,Cin,3,3] weight with Cout %% 16 == 0 and Cin %% 16 == 0 expected (got %s)'
+                           % (tuple(w.shape),))
+    out = torch.empty(n, dtype=torch.float32, device=w.device)
+    _lib.check(lib.ct_pack_conv_weight_s2t(w.data_ptr(), out.data_ptr(), Cout, Cin, _lib.stream_ptr()), 'ct_pack_conv_weight_s2t')
+    return out
+
+
+def conv_s2_backward(x, gy, w=None, need_x=True, need_w=True, gx=None):
+    """Gradients of ``conv3x3(x, w, stride 2, pad 1)`` for the output gradient ``gy`` (NHWC views; ``w``: the OIHW weight,
+    packed here, needed for ``need_x``; ``x`` is read for ``need_w`` only but gives the shape) -> ``(gx view, gw OIHW)``, None
+    for what was not asked for: no buffer is allocated and no kernel runs for those.  ``gx``: a caller-owned view for the input
+    gradient.  Bitwise reproducible."""
+    lib = _lib.load()
+    dev = gy.buf.device
+    if (gy.N, gy.H * 2, gy.W * 2) != (x.N, x.H, x.W):
+        raise _lib.CTError('conv_s2_backward: x is %s pixels, gy %s' % ((x.N, x.H, x.W), (gy.N, gy.H, gy.W)))
+    if not (need_x or need_w):
+        return None, None
+    d = _lib.ConvS2BwdDesc()
+    d.x, d.N, d.H, d.W, d.Cin, d.ldx = x.ptr, x.N, x.H, x.W, x.C, x.ld
+    d.gy, d.Cout, d.ldgy = gy.ptr, gy.C, gy.ld
+    gw = wp = ws = None
+    if need_x:
+        if w is None:
+            raise _lib.CTError('conv_s2_backward: the input gradient needs the weight')
+        wp = pack_weight_s2t(w)
+        if gx is None:
+            gx = new_view(x.N, x.H, x.W, x.C, dev)
+        d.w_s2t, d.gx, d.ldgx = wp.data_ptr(), gx.ptr, gx.ld
+    else:
+        gx = None
+    if need_w:
+        need = lib.ct_conv2d_s2_backward_workspace_bytes(ctypes.byref(d))
+        if not need:
+            raise _lib.CTError('ct_conv2d_s2_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
+        gw = torch.empty((gy.C, x.C, 3, 3), dtype=torch.float32, device=dev)
+        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        d.gw, d.workspace, d.workspace_bytes = gw.data_ptr(), ws.data_ptr(), need
+    _lib.check(lib.ct_conv2d_s2_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_conv2d_s2_backward')
+    return gx, gw
+
+
+def _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, batch_stats=False):
+    d = _lib.BnActDesc()
+    d.z, d.N, d.H, d.W, d.C, d.ldz = z.ptr, z.N, z.H, z.W, z.C, z.ld
+    d.mean, d.invstd, d.gamma, d.beta = (_bn_vec(t, z.C, z).data_ptr() for t in (mean, invstd, gamma, beta))
+    if res is not None:
+        if (res.N, res.H, res.W, res.C) != (z.N, z.H, z.W, z.C):
+            raise _lib.CTError('batch norm: the residual does not have the shape of z')
+        d.res, d.ldr = res.ptr, res.ld
+    d.flags = (_lib.CT_BN_ACT_RELU if relu else 0) | (_lib.CT_BN_BATCH_STATS if batch_stats else 0)
+    return d
+
+
+def bn_act_apply(z, mean, invstd, gamma, beta, res=None, relu=True, out=None):
+    """y = fma(z, a, b) (+ res) (max 0), a = gamma * invstd, b = fma(-mean, a, beta) on NHWC views; allocates ``out`` if not
+    given."""
+    lib = _lib.load()
+    if out is None:
+        out = new_view(z.N, z.H, z.W, z.C, z.buf.device)
+    d = _bn_act_desc(z, mean, invstd, gamma, beta, res, relu)
+    d.y, d.ldy = out.ptr, out.ld
+    _lib.check(lib.ct_bn_act_apply(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_act_apply')
+    return out
+
+
+def bn_act_backward(z, gy, mean, invstd, gamma, beta, batch_stats, res=None, relu=True, need_z=True, need_res=False,
+                    need_gamma=True, need_beta=True):
+    """Gradients of ``bn_act_apply`` (with ``batch_stats``: through the batch statistics as well) for the output gradient
+    ``gy`` -> ``(gz view, gres view, ggamma, gbeta)``, None for what was not asked for.  ``res``: the forward's residual (it
+    decides the ReLU mask).  Bitwise reproducible."""
+    lib = _lib.load()
+    dev = z.buf.device
+    if not (need_z or need_res or need_gamma or need_beta):
+        return None, None, None, None
+    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
+        raise _lib.CTError('bn_act_backward: gy does not have the shape of z')
+    d = _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, batch_stats)
+    d.gy, d.ldgy = gy.ptr, gy.ld
+    gz = new_view(z.N, z.H, z.W, z.C, dev) if need_z else None
+    gr = new_view(z.N, z.H, z.W, z.C, dev) if need_res else None
+    gg = torch.empty(z.C, dtype=torch.float32, device=dev) if need_gamma else None
+    gb = torch.empty(z.C, dtype=torch.float32, device=dev) if need_beta else None
+    if gz is not None:
+        d.gz, d.ldgz = gz.ptr, gz.ld
+    if gr is not None:
+        d.gres, d.ldgres = gr.ptr, gr.ld
+    d.ggamma, d.gbeta = _p(gg), _p(gb)
+    if need_gamma or need_beta or (batch_stats and need_z):
+        need = lib.ct_bn_act_workspace_bytes(ctypes.byref(d))
+        if not need:
+            raise _lib.CTError('ct_bn_act_workspace_bytes: %s' % lib.ct_last_error().decode())
+        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    _lib.check(lib.ct_bn_act_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_act_backward')
+    return gz, gr, gg, gb
+
+
+def maxpool2x2_backward(x, gy, add=None, out=None):
+    """Backward of ``maxpool2x2``: ``x`` the pool's input, ``gy`` the gradient of its output (NHWC views) -> the view ``gx``;
+    each window's gradient goes to its first maximum in row-major order; ``add`` (a view of the shape of ``x``) is summed in."""
+    if (gy.N, gy.H * 2, gy.W * 2, gy.C) != (x.N, x.H, x.W, x.C) or (add is not None and (add.N, add.H, add.W, add.C) != (x.N, x.H, x.W, x.C)):
+        raise _lib.CTError('maxpool2x2_backward: x %s, gy %s do not fit' % ((x.N, x.H, x.W, x.C), (gy.N, gy.H, gy.W, gy.C)))
+    if out is None:
+        out = new_view(x.N, x.H, x.W, x.C, x.buf.device)
+    _lib.check(_lib.load().ct_maxpool2x2_backward(x.ptr, x.N, x.H, x.W, x.C, x.ld, gy.ptr, gy.ld, None if add is None else add.ptr,
+                                                  0 if add is None else add.ld, out.ptr, out.ld, _lib.stream_ptr()),
+               'ct_maxpool2x2_backward')
+    return out
+
+
 # field order of a packed decode row after (score, cls, xs0, ys0)
 _DECODE_REST = ['tracking', 'dep', 'rot', 'dim', 'amodel_offset', 'nuscenes_att', 'velocity']
 

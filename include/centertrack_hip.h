@@ -407,6 +407,73 @@ size_t ct_upsample_add_backward_workspace_bytes(const ct_upsample_bwd_desc *d);
  * gradient of ct_dcn_v2_backward (om = the forward's map, mask after the sigmoid) */
 int ct_dcn_mask_sigmoid_backward(float *g, int ldg, const float *om, int ldom, int N, int H, int W, void *stream);
 
+/* ---- the trainable backbone (BasicBlock / Root / Tree / DLA, dla.py:38-66,154-316); additions under ABI 103.  All fp32 on NHWC
+ * views with a channel pitch under the rules of the neck block above (C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, channel
+ * slices allowed, a view below 2 GiB).  No atomics: every sum has a fixed order, slab counts depend on the shapes only, every
+ * result is bitwise equal from run to run.  The unit of the backbone is conv (ks 1 | 3, stride 1 | 2, no bias) -> BatchNorm
+ * (-> + residual) (-> ReLU); its forward is ct_conv2d + ct_bn_stats + ct_bn_act_apply, its backward ct_bn_act_backward, then
+ * ct_conv2d_backward_weight and a ct_conv2d with the transposed, flipped weight (stride 1) or ct_conv2d_s2_backward (stride 2).
+ *
+ * ct_conv2d_s2_backward: the gradients of y = conv3x3(x, w, stride 2, pad 1), H and W even, Cin % 16 == 0, Cout % 16 == 0.
+ *   x: [N,H,W,Cin] (needed for gw); gy: [N,H/2,W/2,Cout]; gx: [N,H,W,Cin] or NULL; gw: OIHW [Cout,Cin,3,3] or NULL.
+ *   gx[n,iy,ix,ci] = sum gy[n,oy,ox,co] * w[co,ci,ky,kx] over iy + 1 - ky = 2 oy, ix + 1 - kx = 2 ox -- on the fp32 MFMA at the
+ *     forward's flop count: cell (cy,cx) of the output grid owns the input pixels (2cy+a, 2cx+b), which read gy at (cy..cy+1,
+ *     cx..cx+1) only; per axis a = 0 meets tap 1 at cy, a = 1 tap 2 at cy and tap 0 at cy + 1, so the nine taps appear once per
+ *     cell; gy outside the map counts as zero.  Needs w_s2t = ct_pack_conv_weight_s2t(w): [tap][Cout/4][Cin/16][64 lanes],
+ *     lane l = w[co = 4*k4 + (l>>4)][ci = 16*c16 + (l&15)][tap] (ct_packed_conv_weight_s2t_elems(Cout, Cin) = 9*Cout*Cin floats).
+ *   gw[co,ci,ky,kx] = sum_{n,oy,ox} gy[n,oy,ox,co] * x[n,2oy-1+ky,2ox-1+kx,ci] (zero outside the image): K = N*(H/2)*(W/2) in
+ *     slabs to `workspace` (ct_conv2d_s2_backward_workspace_bytes(d) bytes, 0 for a rejected descriptor; not needed for gx
+ *     alone), a second launch adds the slabs in slab order.
+ *   flags: reserved, 0. */
+typedef struct ct_conv_s2_bwd_desc {
+    const float *x; int N, H, W, Cin, ldx;
+    const float *gy; int Cout, ldgy;
+    const float *w_s2t;
+    float *gx; int ldgx;
+    float *gw;
+    float *workspace; size_t workspace_bytes;
+    int flags;
+} ct_conv_s2_bwd_desc;
+int ct_conv2d_s2_backward(const ct_conv_s2_bwd_desc *d, void *stream);
+size_t ct_conv2d_s2_backward_workspace_bytes(const ct_conv_s2_bwd_desc *d);
+size_t ct_packed_conv_weight_s2t_elems(int Cout, int Cin);   /* 0 unless Cout % 16 == 0 and Cin % 16 == 0 */
+int ct_pack_conv_weight_s2t(const float *w_oihw, float *packed, int Cout, int Cin, void *stream);
+/* ct_bn_act_desc = ct_bn_desc plus an optional residual and an optional ReLU, over one pre-activation map z [N,H,W,C]:
+ *   ct_bn_act_apply:     t = fma(z, a, b), a = gamma * invstd, b = fma(-mean, a, beta) (ct_bn_relu_apply's); y = t + res when
+ *                        res != NULL; y = max(0, y) with CT_BN_ACT_RELU
+ *   ct_bn_act_backward:  g = gy where the recomputed y is > 0, else 0 (torch's ReLU: 0 at exactly 0), or g = gy without the
+ *                        ReLU; gres = g; gbeta, ggamma, gz from g as in ct_bn_relu_backward (CT_BN_BATCH_STATS: through the
+ *                        batch statistics).  gz, gres, ggamma, gbeta may each be NULL (not computed).
+ *   mean / invstd are what the forward used (ct_bn_stats on a ct_bn_desc of the same map, or the running statistics).  With the
+ *   ReLU and no residual y and gz equal ct_bn_relu_apply / _backward bit for bit.  The backward needs
+ *   ct_bn_act_workspace_bytes(d) bytes (0 for a rejected descriptor) whenever it sums: for ggamma, gbeta or a batch-statistics
+ *   gz.  var and eps are not read. */
+#define CT_BN_ACT_RELU 2
+typedef struct ct_bn_act_desc {
+    const float *z; int N, H, W, C, ldz;
+    float *mean; float *var; float *invstd;
+    float eps;
+    const float *gamma; const float *beta;
+    float *y; int ldy;
+    const float *gy; int ldgy;
+    float *gz; int ldgz;
+    float *ggamma; float *gbeta;
+    float *workspace; size_t workspace_bytes;
+    int flags;                                  /* CT_BN_BATCH_STATS | CT_BN_ACT_RELU */
+    const float *res; int ldr;                  /* residual added behind the affine map, or NULL */
+    float *gres; int ldgres;                    /* its gradient (backward), or NULL */
+} ct_bn_act_desc;
+int ct_bn_act_apply(const ct_bn_act_desc *d, void *stream);
+int ct_bn_act_backward(const ct_bn_act_desc *d, void *stream);
+size_t ct_bn_act_workspace_bytes(const ct_bn_act_desc *d);
+/* ct_maxpool2x2_backward: the backward of ct_maxpool2x2 (H, W = the INPUT grid, even).  x: the pool's input [N,H,W,C]; gy:
+ *   [N,H/2,W/2,C]; gx [N,H,W,C]: each window's gradient goes to its first maximum in row-major order (torch's rule: a window of
+ *   equal values sends it to the top-left, -0.0 ties with 0, a NaN wins), the other three elements get 0; `add` (a view of the
+ *   shape of gx, or NULL) is summed in -- a Tree's input gradient is the stride-2 conv's gx plus the pool's.  Every gx element
+ *   is written exactly once. */
+int ct_maxpool2x2_backward(const float *x, int N, int H, int W, int C, int ldx, const float *gy, int ldgy,
+                           const float *add, int ldadd, float *gx, int ldgx, void *stream);
+
 /* ---- the three 7x7 stems, fused --------------------------------------------------
  * Replaces DLA.forward's base_layer / pre_img_layer / pre_hm_layer and their sum
  * (dla.py:238-267,305-311): y = sum_s relu(bn_s(conv7x7_s(in_s))), inputs NCHW
