@@ -15,7 +15,7 @@
 //     couts) block and one K slab of output pixels, its four waves split the slab, are summed through LDS in wave order and
 //     the partial block goes to slab `blockIdx.y` of the workspace; s2_slab_reduce_kernel adds the slabs in slab order.
 //   * bn_act_reduce_kernel / bn_act_finalize_kernel / bn_act_apply_kernel / bn_act_bwd_kernel: the kernels of neck_bwd.hip
-//     (same plan, same order of every sum, same bn_affine) with y = fma(z, a, b) (+ res) (max 0), the mask recomputed from
+//     (same plan, same order of every sum, same bn_pre) with y = fma(z - mean, a, beta) (+ res) (max 0), the mask recomputed from
 //     the same bits, and gres = g.  With the ReLU and no residual the results are those of ct_bn_relu_* bit for bit.
 //   * maxpool_bwd_kernel: thread = one 2x2 window and channel quad; the window's gradient goes to its first maximum in
 //     row-major order (torch's rule: a later value wins only if it is greater or NaN), the other three get 0, plus `add`.
@@ -41,12 +41,9 @@ __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, int voff)
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
 }
 
-// the affine form of BatchNorm that forward and backward share (neck_bwd.hip's)
-__device__ __forceinline__ void bn_affine(float gamma, float beta, float mean, float invstd, float &a, float &b)
-{
-    a = gamma * invstd;
-    b = fmaf(-mean, a, beta);
-}
+// the pre-activation of BatchNorm that forward and backward share, a = gamma * invstd (neck_bwd.hip's, which says why the
+// difference comes first)
+__device__ __forceinline__ float bn_pre(float z, float mean, float a, float beta) { return fmaf(z - mean, a, beta); }
 
 bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
@@ -316,10 +313,10 @@ struct BnActArgs {
 };
 
 // the incoming gradient behind the activation: the forward's own bits decide the mask (torch's ReLU: 0 at exactly 0)
-__device__ __forceinline__ float act_grad(const BnActArgs &a, float z, float ka, float kb, float r, float gy)
+__device__ __forceinline__ float act_grad(const BnActArgs &a, float z, float mean, float ka, float beta, float r, float gy)
 {
     if (!a.relu) return gy;
-    float t = fmaf(z, ka, kb);
+    float t = bn_pre(z, mean, ka, beta);
     if (a.res) t += r;
     return t > 0.0f ? gy : 0.0f;
 }
@@ -334,21 +331,16 @@ __global__ __launch_bounds__(256) void bn_act_reduce_kernel(BnActArgs a)
     if (live) {
         const int p0 = (int)blockIdx.x * a.pixPerSlab, p1 = min(a.P, p0 + a.pixPerSlab);
         const f32x4 mean = ld4(a.mean + c), istd = ld4(a.invstd + c), ga = ld4(a.gamma + c), be = ld4(a.beta + c);
-        f32x4 ka, kb;
+        f32x4 ka;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float sa, sb;
-            bn_affine(ga[i], be[i], mean[i], istd[i], sa, sb);
-            ka[i] = sa;
-            kb[i] = sb;
-        }
+        for (int i = 0; i < 4; ++i) ka[i] = ga[i] * istd[i];
         for (int p = p0 + r; p < p1; p += a.rows) {
             const f32x4 z = ld4(a.z + p * a.ldz + c), gy = ld4(a.gy + p * a.ldgy + c);
             f32x4 rv = {0.f, 0.f, 0.f, 0.f};
             if (a.res) rv = ld4(a.res + p * a.ldr + c);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float g = act_grad(a, z[i], ka[i], kb[i], rv[i], gy[i]);
+                const float g = act_grad(a, z[i], mean[i], ka[i], be[i], rv[i], gy[i]);
                 const float xh = (z[i] - mean[i]) * istd[i];
                 s0[i] += g;
                 s1[i] = fmaf(g, xh, s1[i]);
@@ -400,9 +392,7 @@ __global__ __launch_bounds__(256) void bn_act_apply_kernel(BnActArgs a)
         f32x4 y;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float ka, kb;
-            bn_affine(ga[i], be[i], mean[i], istd[i], ka, kb);
-            float t = fmaf(z[i], ka, kb);
+            float t = bn_pre(z[i], mean[i], ga[i] * istd[i], be[i]);
             if (a.res) t += rv[i];
             y[i] = a.relu ? fmaxf(t, 0.0f) : t;
         }
@@ -429,9 +419,8 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(BnActArgs a)
         f32x4 gz, gr;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float ka, kb;
-            bn_affine(ga[i], be[i], mean[i], istd[i], ka, kb);
-            const float g = act_grad(a, z[i], ka, kb, rv[i], gy[i]);
+            const float ka = ga[i] * istd[i];
+            const float g = act_grad(a, z[i], mean[i], ka, be[i], rv[i], gy[i]);
             gr[i] = g;
             if (a.batchStats) {
                 const float xh = (z[i] - mean[i]) * istd[i];

@@ -9,8 +9,8 @@
 //     `blockIdx.x` of the workspace.  bn_finalize_kernel<MODE> adds the slabs in slab order.
 //       MODE 0: sum (z - z[pixel 0]) -> mean.  MODE 1: sum (z - mean)^2 -> biased variance, invstd (two passes, never E[x^2] - E[x]^2).
 //       MODE 2: sum g and sum g * xhat with g = gy where the recomputed pre-activation is > 0 -> gbeta, ggamma.
-//   * bn_relu_apply_kernel: y = max(0, fma(z, a, b)), a = gamma * invstd, b = fma(-mean, a, beta) (bn_affine below: the
-//     backward recomputes the same bits from the same four vectors).
+//   * bn_relu_apply_kernel: y = max(0, fma(z - mean, a, beta)), a = gamma * invstd (bn_pre below: the backward recomputes
+//     the same bits from the same four vectors).
 //   * bn_relu_bwd_kernel: gz = a * (g - mean(g) - xhat * mean(g * xhat)) with batch statistics, a * g with running ones.
 //   * up_gx_kernel: gx[n,iy,ix,c] = sum_{ky,kx < 2f} gy[n, iy*f - f/2 + ky, ix*f - f/2 + kx, c] * w[ky,kx,c], a gather in
 //     tap order.  up_gw_kernel<F>: gw[c,ky,kx] = sum_{n,iy,ix} x * gy; a workgroup owns a slab of input pixels and 16
@@ -28,12 +28,11 @@ const double VIEW_LIMIT = 2147483648.0;
 __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 
-// the affine form of BatchNorm that forward and backward share
-__device__ __forceinline__ void bn_affine(float gamma, float beta, float mean, float invstd, float &a, float &b)
-{
-    a = gamma * invstd;
-    b = fmaf(-mean, a, beta);
-}
+// The pre-activation of BatchNorm that forward and backward share, a = gamma * invstd.  The difference comes first: z - mean
+// is exact where z lies within a factor of two of the mean, so what is left of a channel with |mean| >> std is the rounding
+// of the fp32 mean itself times a.  The folded form fma(z, a, fma(-mean, a, beta)) rounds the shift at the size of mean * a
+// on top of that: at mean 100, std 0.01 half an ulp of 1e4, 5e-4 of a pre-activation of order 1.
+__device__ __forceinline__ float bn_pre(float z, float mean, float a, float beta) { return fmaf(z - mean, a, beta); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // BatchNorm
@@ -57,19 +56,15 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnArgs a)
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
     if (live) {
         const int p0 = (int)blockIdx.x * a.pixPerSlab, p1 = min(a.P, p0 + a.pixPerSlab);
-        f32x4 mean = {0.f, 0.f, 0.f, 0.f}, istd = mean, ka = mean, kb = mean;
+        f32x4 mean = {0.f, 0.f, 0.f, 0.f}, istd = mean, ka = mean, be = mean;
         if (MODE == 0) mean = ld4(a.z + c);                      // the pivot: pixel 0 of the view (a sum of z - pivot keeps
         if (MODE >= 1) mean = ld4(a.mean + c);                  // a channel of mean 100, std 0.01 exact where a sum of z loses it)
         if (MODE == 2) {
             istd = ld4(a.invstd + c);
-            const f32x4 ga = ld4(a.gamma + c), be = ld4(a.beta + c);
+            const f32x4 ga = ld4(a.gamma + c);
+            be = ld4(a.beta + c);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float sa, sb;
-                bn_affine(ga[i], be[i], mean[i], istd[i], sa, sb);
-                ka[i] = sa;
-                kb[i] = sb;
-            }
+            for (int i = 0; i < 4; ++i) ka[i] = ga[i] * istd[i];
         }
         for (int p = p0 + r; p < p1; p += a.rows) {
             const f32x4 z = ld4(a.z + p * a.ldz + c);
@@ -86,7 +81,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnArgs a)
                 const f32x4 gy = ld4(a.gy + p * a.ldgy + c);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float g = fmaf(z[i], ka[i], kb[i]) > 0.0f ? gy[i] : 0.0f;      // torch's ReLU: 0 at exactly 0
+                    const float g = bn_pre(z[i], mean[i], ka[i], be[i]) > 0.0f ? gy[i] : 0.0f;      // torch's ReLU: 0 at exactly 0
                     const float xh = (z[i] - mean[i]) * istd[i];
                     s0[i] += g;
                     s1[i] = fmaf(g, xh, s1[i]);
@@ -148,9 +143,7 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(BnArgs a)
         f32x4 y;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float ka, kb;
-            bn_affine(ga[i], be[i], mean[i], istd[i], ka, kb);
-            y[i] = fmaxf(fmaf(z[i], ka, kb), 0.0f);
+            y[i] = fmaxf(bn_pre(z[i], mean[i], ga[i] * istd[i], be[i]), 0.0f);
         }
         st4(a.y + p * a.ldy + c, y);
     }
@@ -173,9 +166,8 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_kernel(BnArgs a)
         f32x4 gz;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float ka, kb;
-            bn_affine(ga[i], be[i], mean[i], istd[i], ka, kb);
-            const float g = fmaf(z[i], ka, kb) > 0.0f ? gy[i] : 0.0f;
+            const float ka = ga[i] * istd[i];
+            const float g = bn_pre(z[i], mean[i], ka, be[i]) > 0.0f ? gy[i] : 0.0f;
             if (a.batchStats) {
                 const float xh = (z[i] - mean[i]) * istd[i];
                 gz[i] = ka * ((g - sg[i] * invP) - xh * (sgx[i] * invP));

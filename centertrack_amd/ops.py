@@ -550,7 +550,7 @@ def bn_stats(z, eps=1e-5):
 
 
 def bn_relu_apply(z, mean, invstd, gamma, beta, out=None):
-    """y = max(0, fma(z, a, b)), a = gamma * invstd, b = fma(-mean, a, beta) on NHWC views; allocates ``out`` if not given."""
+    """y = max(0, fma(z - mean, a, beta)), a = gamma * invstd on NHWC views; allocates ``out`` if not given."""
     lib = _lib.load()
     if out is None:
         out = new_view(z.N, z.H, z.W, z.C, z.buf.device)
@@ -688,7 +688,7 @@ def _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, batch_stats=False):
 
 
 def bn_act_apply(z, mean, invstd, gamma, beta, res=None, relu=True, out=None):
-    """y = fma(z, a, b) (+ res) (max 0), a = gamma * invstd, b = fma(-mean, a, beta) on NHWC views; allocates ``out`` if not
+    """y = fma(z - mean, a, beta) (+ res) (max 0), a = gamma * invstd on NHWC views; allocates ``out`` if not
     given."""
     lib = _lib.load()
     if out is None:

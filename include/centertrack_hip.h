@@ -363,7 +363,7 @@ size_t ct_heads_tail_backward_workspace_bytes(const ct_heads_tail_bwd_desc *d);
  *
  * ct_bn_desc serves three calls over one pre-activation map z [N,H,W,C]:
  *   ct_bn_stats:          mean[c], var[c] (biased, two passes: sum of z - z[pixel 0], then sum of squared deviations), invstd[c] = 1/sqrt(var + eps)
- *   ct_bn_relu_apply:     y = max(0, fma(z, a, b)), a = gamma * invstd, b = fma(-mean, a, beta)
+ *   ct_bn_relu_apply:     y = max(0, fma(z - mean, a, beta)), a = gamma * invstd
  *   ct_bn_relu_backward:  g = gy where the recomputed pre-activation is > 0, else 0 (torch's ReLU: 0 at exactly 0);
  *                         gbeta = sum g, ggamma = sum g * xhat, xhat = (z - mean) * invstd;
  *                         gz = a * (g - mean(g) - xhat * mean(g * xhat)) with CT_BN_BATCH_STATS, a * g without
@@ -439,7 +439,7 @@ size_t ct_conv2d_s2_backward_workspace_bytes(const ct_conv_s2_bwd_desc *d);
 size_t ct_packed_conv_weight_s2t_elems(int Cout, int Cin);   /* 0 unless Cout % 16 == 0 and Cin % 16 == 0 */
 int ct_pack_conv_weight_s2t(const float *w_oihw, float *packed, int Cout, int Cin, void *stream);
 /* ct_bn_act_desc = ct_bn_desc plus an optional residual and an optional ReLU, over one pre-activation map z [N,H,W,C]:
- *   ct_bn_act_apply:     t = fma(z, a, b), a = gamma * invstd, b = fma(-mean, a, beta) (ct_bn_relu_apply's); y = t + res when
+ *   ct_bn_act_apply:     t = fma(z - mean, a, beta), a = gamma * invstd (ct_bn_relu_apply's); y = t + res when
  *                        res != NULL; y = max(0, y) with CT_BN_ACT_RELU
  *   ct_bn_act_backward:  g = gy where the recomputed y is > 0, else 0 (torch's ReLU: 0 at exactly 0), or g = gy without the
  *                        ReLU; gres = g; gbeta, ggamma, gz from g as in ct_bn_relu_backward (CT_BN_BATCH_STATS: through the

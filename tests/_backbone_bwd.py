@@ -15,12 +15,29 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
+import _neck_bwd
 from _dcn_bwd import bound, cdiv, err, randn  # noqa: F401  (the project's error measure and bound)
-from _neck_bwd import BN_SHAPES, EPS, MOMENTUM, bn_plan, cast, grads, is_buffer  # noqa: F401
+from _neck_bwd import (BN_PLAN_SHAPES, BN_REGIMES, BN_SHAPES, EPS, EW_CAP, MOMENTUM, bn_plan, cast, ew_plan, grads,  # noqa: F401
+                       is_buffer, missing_bn_regimes, reached, reached_bn_regimes)
 
 S2_SHAPES = [(2, 6, 10, 16, 32), (1, 4, 4, 64, 128), (3, 2, 2, 256, 512), (1, 34, 66, 32, 64)]     # (N, H, W, Cin, Cout)
 POOL_SHAPES = [(2, 6, 10, 16), (1, 2, 2, 132), (1, 34, 66, 8)]                                  # (N, H, W, C)
 DLA34 = dict(levels=[1, 1, 1, 2, 2, 1], channels=[16, 32, 64, 128, 256, 512])
+
+# The shapes above keep the slab count of the weight gradient at ``maxSlabs`` and every element-wise grid below its cap.
+# What production training and the API reach beyond that (tests/test_backbone_backward_cpu.py holds the lists against
+# ``missing_*_regimes``), each the smallest shape of its kind:
+#   (2,96,100,64,128)   29 slabs from cdiv(1024, 36 units); stepsPerWave 11 (% 4 == 3); 1200 steps over 116 waves: six waves
+#                       and one whole slab idle (the slab must still write zeros); two images of 2400 output pixels: no
+#                       4-pixel step crosses the image border; Wo 50, Ho 48: ragged in x only
+#   (1,64,72,256,512)   2 slabs from the target (576 units), stepsPerWave 36; eight cout groups, eight LDS chunks in gx
+#   (1,6,10,48,80)      Cin % 32 == 16 with two channel groups (``has1`` false with cig > 0); Cout 80: a partial second LDS
+#                       chunk of 16 couts in gx, a second cout group of ONE tile in gw (nco 1 with cog > 0)
+#   (1,8,32,16,16)      Wo 16, Ho 4: one tile whose halo row and column lie wholly outside the map
+S2_PLAN_SHAPES = [(2, 96, 100, 64, 128), (1, 64, 72, 256, 512), (1, 6, 10, 48, 80), (1, 8, 32, 16, 16)]
+#   (3,256,260,44)      3 * 128 * 130 windows * 11 quads = 549 120 >= 2048 * 256 and no multiple of it: the grid is capped;
+#                       11 quads per pixel: the split of the index is a real division
+POOL_PLAN_SHAPES = [(3, 256, 260, 44)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -28,15 +45,86 @@ DLA34 = dict(levels=[1, 1, 1, 2, 2, 1], channels=[16, 32, 64, 128, 256, 512])
 
 def s2_plan(N, H, W, Cin, Cout):
     """make_s2_plan: the input gradient runs one workgroup per (image, 4 x 16 cells, 32 input channels); the weight gradient
-    one per (tap, 32 input channels, 64 couts) and K slab of output pixels; workspace = slabs * Cout * Cin * 9 floats"""
+    one per (tap, 32 input channels, 64 couts) and K slab of output pixels; workspace = slabs * Cout * Cin * 9 floats.
+    ``wanted`` = the grid target, ``maxSlabs`` = the pixel limit; then what follows inside conv_s2_gw_kernel (wave j of the
+    slabs * 4 runs steps j * stepsPerWave .. of ``nsteps``: the waves and slabs past the end are idle) and conv_s2_gx_kernel."""
     Ho, Wo = H // 2, W // 2
     cgroups = cdiv(Cin, 32)
     gx_units = N * cdiv(Wo, 16) * cdiv(Ho, 4) * cgroups
-    gw_units = 9 * cgroups * cdiv(Cout // 16, 4)
+    NT = Cout // 16
+    cogroups = cdiv(NT, 4)
+    gw_units = 9 * cgroups * cogroups
     nsteps = cdiv(N * Ho * Wo, 4)
-    slabs = max(1, min(cdiv(1024, gw_units), cdiv(nsteps, 32)))
-    return dict(gx_units=gx_units, gw_units=gw_units, slabs=slabs, stepsPerWave=cdiv(nsteps, slabs * 4),
-                bytes=slabs * Cout * Cin * 9 * 4)
+    wanted, maxSlabs = cdiv(1024, gw_units), cdiv(nsteps, 32)
+    slabs = max(1, min(wanted, maxSlabs))
+    spw = cdiv(nsteps, slabs * 4)
+    return dict(gx_units=gx_units, gw_units=gw_units, slabs=slabs, stepsPerWave=spw, bytes=slabs * Cout * Cin * 9 * 4,
+                Ho=Ho, Wo=Wo, cgroups=cgroups, cogroups=cogroups, nco_last=NT - (cogroups - 1) * 4, nsteps=nsteps,
+                wanted=wanted, maxSlabs=maxSlabs, capped=wanted > maxSlabs, idle_waves=slabs * 4 - cdiv(nsteps, spw),
+                idle_slabs=slabs - cdiv(nsteps, spw * 4))
+
+
+def pool_plan(N, H, W, C):
+    """the grid of maxpool_bwd_kernel: one thread per 2x2 window and channel quad"""
+    return ew_plan(N * (H // 2) * (W // 2) * (C // 4))
+
+
+def _s2_regimes():
+    """name -> predicate over ((N, H, W, Cin, Cout), plan): what make_s2_plan and the two kernels branch on"""
+    r = OrderedDict()
+    r['slabs cut by maxSlabs'] = lambda s, p: p['capped']
+    r['slabs from cdiv(1024, units)'] = lambda s, p: not p['capped']
+    r['slabs == 1'] = lambda s, p: p['slabs'] == 1
+    for m in (0, 1, 2, 3):
+        r['stepsPerWave %% 4 == %d' % m] = lambda s, p, m=m: p['stepsPerWave'] % 4 == m
+    r['a whole idle wave'] = lambda s, p: p['idle_waves'] >= 1
+    r['a whole idle slab'] = lambda s, p: p['idle_slabs'] >= 1
+    r['stepsPerWave >= 32 with slabs from the target'] = lambda s, p: not p['capped'] and p['stepsPerWave'] >= 32
+    r['nco < 4 in a cout group other than the first'] = lambda s, p: p['cogroups'] > 1 and p['nco_last'] < 4
+    r['Cin % 32 == 16 with more than one channel group'] = lambda s, p: s[3] % 32 == 16 and p['cgroups'] > 1
+    r['Cout % 64 != 0 with Cout > 64'] = lambda s, p: s[4] > 64 and s[4] % 64 != 0
+    r['Wo % 16 == 0 and Ho % 4 == 0'] = lambda s, p: p['Wo'] % 16 == 0 and p['Ho'] % 4 == 0
+    r['Wo == 16 and Ho == 4: the halo lies wholly outside the map'] = lambda s, p: p['Wo'] == 16 and p['Ho'] == 4
+    r['ragged tiles on both axes'] = lambda s, p: p['Wo'] % 16 != 0 and p['Ho'] % 4 != 0
+    r['N >= 2, a 4-pixel step crosses an image border'] = lambda s, p: s[0] >= 2 and (p['Ho'] * p['Wo']) % 4 != 0
+    r['N >= 2, no 4-pixel step crosses an image border'] = lambda s, p: s[0] >= 2 and (p['Ho'] * p['Wo']) % 4 == 0
+    return r
+
+
+def _pool_regimes():
+    r = OrderedDict()
+    r['grid uncapped'] = lambda s, p: not p['ew_capped']
+    r['grid capped'] = lambda s, p: p['ew_capped']
+    r['grid capped, total not a multiple of 2048 * 256'] = lambda s, p: p['ew_ragged']
+    return r
+
+
+S2_REGIMES, POOL_REGIMES = _s2_regimes(), _pool_regimes()
+
+
+def reached_s2_regimes(shapes):
+    return reached(S2_REGIMES, [(s, s2_plan(*s)) for s in shapes])
+
+
+def reached_pool_regimes(shapes):
+    return reached(POOL_REGIMES, [(s, pool_plan(*s)) for s in shapes])
+
+
+def missing_s2_regimes(shapes):
+    """names of the stride-2 regimes no (N, H, W, Cin, Cout) of the list reaches"""
+    got = reached_s2_regimes(shapes)
+    return [name for name in S2_REGIMES if name not in got]
+
+
+def missing_pool_regimes(shapes):
+    """names of the max-pool regimes no (N, H, W, C) of the list reaches"""
+    got = reached_pool_regimes(shapes)
+    return [name for name in POOL_REGIMES if name not in got]
+
+
+def gpu_bn_shapes():
+    """every (N, H, W, C) the BatchNorm-act op tests of tests/test_hip_backbone_backward.py run"""
+    return list(BN_SHAPES) + list(BN_PLAN_SHAPES)
 
 
 def dla_units(N, H, W, levels=None, channels=None):
@@ -115,6 +203,40 @@ def tie_fraction(x):
     """share of the 2x2 windows whose maximum is reached more than once"""
     v = torch.stack([x[:, :, 0::2, 0::2], x[:, :, 0::2, 1::2], x[:, :, 1::2, 0::2], x[:, :, 1::2, 1::2]])
     return float(((v == v.max(0).values).sum(0) > 1).double().mean())
+
+
+def tie_input(seed, N, C, H, W):
+    """a post-ReLU map (fp32): most windows all zero, one of equal positive values, -0.0 in front of and behind a 0"""
+    x = torch.relu(randn(seed, N, C, H, W) - 1.0)
+    x[:, :, 0:2, 0:2] = 0.75
+    x[:, 0::2, -2, -2] = -0.0
+    x[:, 1::2, -1, -1] = -0.0
+    return x.float()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of the op tests
+
+def bn_case(shape):
+    """``_neck_bwd.bn_case`` plus a residual"""
+    return _neck_bwd.bn_case(shape, residual=True)
+
+
+_s2_cache = {}
+
+
+def s2_case(shape):
+    """fp32 (x, w, gy) of a (N, H, W, Cin, Cout) and {dtype: (gx, gw)} of torch autograd on the CPU, once per process"""
+    if shape not in _s2_cache:
+        N, H, W, Cin, Cout = shape
+        x, w = randn(11, N, Cin, H, W).float(), (randn(12, Cout, Cin, 3, 3) * (9 * Cin) ** -0.5).float()
+        gy = randn(13, N, Cout, H // 2, W // 2).float()
+        ref = {}
+        for dt in (torch.float64, torch.float32):
+            xt, wt = x.to(dt).clone().requires_grad_(), w.to(dt).clone().requires_grad_()     # (the fp32 ``.to`` is x itself)
+            ref[dt] = torch.autograd.grad(F.conv2d(xt, wt, None, 2, 1), (xt, wt), gy.to(dt))
+        _s2_cache[shape] = (x, w, gy, ref)
+    return _s2_cache[shape]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

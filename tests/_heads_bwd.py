@@ -136,4 +136,82 @@ def tail_plan(N, H, W, hc, cs):
     slabs = cdiv(total, pps)
     stride = sum(c * (hc + 1) for c in cs)
     return dict(kblocks=kblocks, passes=[cdiv(c, 16) for c in cs], slabs=slabs, pixPerSlab=pps,
-                last_slab_pixels=total - (slabs - 1) * pps, slabStride=stride, bytes=slabs * stride * 4)
+                last_slab_pixels=total - (slabs - 1) * pps, slabStride=stride, bytes=slabs * stride * 4,
+                wanted=cdiv(2048, wgs), maxSlabs=cdiv(total, 64), capped=cdiv(2048, wgs) > cdiv(total, 64))
+
+
+# The tail at two tiles per slab.  In ``SHAPES`` the pixel limit always wins and ``pixPerSlab`` is 64, one tile: the tile loop
+# of heads_tail_weight_kernel runs once.  Sixteen heads of width 20 on (2, 41, 51): 32 workgroups per slab, 64 slabs wanted
+# of 66 possible, ``pixPerSlab`` 128 -- two tiles, ``g`` re-staged between them and ``bsum`` carried across -- 33 slabs, the
+# last one 86 pixels = a full tile and a ragged one of 22; images of 2091 pixels, so tile 32 of the 66 crosses the image
+# border.  (Training at batch 4 on 512 x 512 runs ``pixPerSlab`` 128 as well.)  The hidden map is built directly, see
+# ``tail_fixture``.
+TAIL_CASE = ((2, 41, 51), OrderedDict(('h%02d' % i, 20) for i in range(16)))
+
+
+def tail_cases():
+    """every ((N, H, W), heads) the GPU tests run through ct_heads_tail_backward"""
+    return list(SHAPES) + [TAIL_CASE]
+
+
+def _tail_regimes():
+    """name -> predicate over (((N, H, W), heads), tail plan): what make_tail_plan and the two tail kernels branch on"""
+    r = OrderedDict()
+    r['slabs cut by the pixels'] = lambda s, p: p['capped']
+    r['slabs from the grid target'] = lambda s, p: not p['capped']
+    r['pixPerSlab == 64'] = lambda s, p: p['pixPerSlab'] == 64
+    r['pixPerSlab >= 128'] = lambda s, p: p['pixPerSlab'] >= 128
+    r['a last slab of more than one tile whose last tile is ragged'] = \
+        lambda s, p: p['last_slab_pixels'] > 64 and p['last_slab_pixels'] % 64 != 0
+    r['a last slab of one ragged tile'] = lambda s, p: p['last_slab_pixels'] < 64
+    r['a tile that crosses an image border'] = lambda s, p: s[0][0] >= 2 and (s[0][1] * s[0][2]) % 64 != 0
+    r['a head wider than 16 next to a narrower one'] = lambda s, p: max(p['passes']) > 1 and min(p['passes']) < max(p['passes'])
+    r['every head wider than 16'] = lambda s, p: min(p['passes']) > 1
+    r['kblocks == 1'] = lambda s, p: p['kblocks'] == 1
+    return r
+
+
+TAIL_REGIMES = _tail_regimes()
+
+
+def reached_tail_regimes(cases, hc=HC):
+    plans = [(c, tail_plan(*c[0], hc, tuple(c[1].values()))) for c in cases]
+    return [name for name, pred in TAIL_REGIMES.items() if any(pred(c, p) for c, p in plans)]
+
+
+def missing_tail_regimes(cases, hc=HC):
+    """names of the tail regimes no case of the list reaches"""
+    got = reached_tail_regimes(cases, hc)
+    return [name for name in TAIL_REGIMES if name not in got]
+
+
+def tail_fixture(case, seed=0):
+    """fp32 CPU tensors for the tail alone: the hidden map ``mid`` [N, nheads*hc, H, W] = relu of a Gaussian, built directly
+    (half of it exact zeros: the ReLU mask is taken from ``mid`` itself, as by the kernel), per head w2 [c,hc,1,1] and gout
+    [N,c,H,W], and the first layers' weight w0 [nheads*hc, 64, 3, 3] for the input gradient"""
+    (N, H, W), heads = case
+    nh = len(heads)
+    fx = {'heads': heads, 'mid': torch.relu(torch.randn((N, nh * HC, H, W), generator=_gen(seed + 1))), 'w2': OrderedDict(),
+          'gout': OrderedDict(), 'w0': torch.randn((nh * HC, CIN, 3, 3), generator=_gen(seed + 2)) * (9 * CIN) ** -0.5}
+    for j, (h, c) in enumerate(heads.items()):
+        s = seed + 100 * (j + 1)
+        fx['w2'][h] = torch.randn((c, HC, 1, 1), generator=_gen(s + 3)) * HC ** -0.5
+        fx['gout'][h] = torch.randn((N, c, H, W), generator=_gen(s + 5))
+    return fx
+
+
+def tail_truth(fx, dtype):
+    """the tail's gradients in ``dtype`` as explicit sums: gw2[h] = sum_{n,p} gout[h] x mid[h], gb2[h] = sum gout[h],
+    gmid[h] = (w2[h]^T gout[h]) where mid > 0, and gx = conv3x3 of gmid with w0 transposed -> dict"""
+    mid = fx['mid'].to(dtype)
+    res = {'w2': OrderedDict(), 'b2': OrderedDict()}
+    gm = []
+    for j, h in enumerate(fx['heads']):
+        m = mid[:, HC * j:HC * (j + 1)]
+        g, w2 = fx['gout'][h].to(dtype), fx['w2'][h].to(dtype)
+        res['w2'][h] = torch.einsum('nchw,nkhw->ck', g, m).view(w2.shape)
+        res['b2'][h] = g.sum((0, 2, 3))
+        gm.append(torch.einsum('nchw,ck->nkhw', g, w2[:, :, 0, 0]) * (m > 0).to(dtype))
+    res['gmid'] = torch.cat(gm, 1)
+    res['x'] = F.conv_transpose2d(res['gmid'], fx['w0'].to(dtype), padding=1)
+    return res

@@ -17,30 +17,139 @@ BUFFERS = ('running_mean', 'running_var', 'num_batches_tracked')
 # ---------------------------------------------------------------------------------------------------------------------
 # the launch plans, restated
 
+# ``ew_grid`` of neck_bwd.hip / backbone_bwd.hip launches cdiv(total, 256) workgroups of 256 threads below this many channel
+# quads and 2048 from there on, where the grid-stride loop of the element-wise kernels runs a second time.  The constant is
+# not observable through the ABI: it is mirrored by reading.
+EW_CAP = 2048 * 256
+
+
+def ew_plan(quads):
+    """``ew_grid(quads)`` and what follows from it inside a grid-stride kernel"""
+    capped = quads >= EW_CAP
+    return dict(quads=quads, ew_capped=capped, ew_grid=2048 if capped else cdiv(quads, 256),
+                ew_ragged=capped and quads % EW_CAP != 0)
+
+
 def bn_plan(N, H, W, C):
-    """make_bn_plan: slabs of pixels x chunks of up to 64 channel quads; workspace = (slabs + 1) * 2 * C floats"""
+    """make_bn_plan (neck_bwd.hip; make_bn_act_plan of backbone_bwd.hip is the same arithmetic): slabs of pixels x chunks of up
+    to 64 channel quads; workspace = (slabs + 1) * 2 * C floats.  ``wanted`` = the grid target, ``maxSlabs`` = the pixel limit;
+    the element-wise kernels (apply, backward) run over P * C / 4 quads (``ew_plan``)."""
     P, C4 = N * H * W, C // 4
     cw = min(C4, 64)
     rows = 256 // cw
     chunks = cdiv(C4, cw)
-    slabs = max(1, min(cdiv(512, chunks), cdiv(P, rows * 4)))
+    wanted, maxSlabs = cdiv(512, chunks), cdiv(P, rows * 4)
+    slabs = max(1, min(wanted, maxSlabs))
     pix = cdiv(cdiv(P, slabs), rows) * rows
     slabs = cdiv(P, pix)
-    return dict(cw=cw, rows=rows, chunks=chunks, slabs=slabs, pixPerSlab=pix, bytes=(slabs + 1) * 2 * C * 4)
+    return dict(cw=cw, rows=rows, chunks=chunks, slabs=slabs, pixPerSlab=pix, bytes=(slabs + 1) * 2 * C * 4,
+                wanted=wanted, maxSlabs=maxSlabs, capped=wanted > maxSlabs, last_slab_pixels=P - (slabs - 1) * pix,
+                dead_threads=256 - rows * cw, **ew_plan(P * C4))
 
 
 def up_plan(N, H, W, C, f):
-    """make_up_plan (H, W = the input grid): slabs of input pixels x chunks of 16 channel quads; workspace = slabs * 4f^2 * C"""
+    """make_up_plan (H, W = the input grid): slabs of input pixels x chunks of 16 channel quads; workspace = slabs * 4f^2 * C;
+    ``up_gx_kernel`` runs over Pin * C / 4 quads (``ew_plan``)"""
     Pin = N * H * W
     chunks = cdiv(C // 4, 16)
-    slabs = max(1, min(cdiv(512, chunks), cdiv(Pin, 8)))
+    wanted, maxSlabs = cdiv(512, chunks), cdiv(Pin, 8)
+    slabs = max(1, min(wanted, maxSlabs))
     pix = cdiv(Pin, slabs)
     slabs = cdiv(Pin, pix)
-    return dict(chunks=chunks, slabs=slabs, pixPerSlab=pix, bytes=slabs * 4 * f * f * C * 4)
+    return dict(chunks=chunks, slabs=slabs, pixPerSlab=pix, bytes=slabs * 4 * f * f * C * 4, wanted=wanted, maxSlabs=maxSlabs,
+                capped=wanted > maxSlabs, last_slab_pixels=Pin - (slabs - 1) * pix, f=f, **ew_plan(Pin * (C // 4)))
 
 
 BN_SHAPES = [(2, 5, 7, 64), (3, 9, 11, 132), (1, 33, 65, 8)]
 UP_SHAPES = [(2, 5, 7, 8), (2, 5, 7, 64), (1, 3, 2, 132)]                 # (N, H, W, C) of the input grid, f in {2, 4, 8}
+
+# The shapes above keep every slab count at the pixel limit and every element-wise grid below its cap.  What production
+# training reaches beyond that (tests/test_neck_backward_cpu.py holds the lists against ``missing_*_regimes``), each the
+# smallest shape of its kind:
+#   (3,254,258,16)   512 slabs from the grid target, the last one 372 of 384 pixels; 786 384 quads: the element-wise grid is
+#                    capped and the second round of its loop is ragged
+#   (1,66,70,512)    two chunks, 231 slabs from the target (256), 591 360 quads
+#   (2,90,94,132)    cw 33: 25 dead threads per workgroup, 484 slabs from the target, 558 360 quads
+#   (1,12,20,16)     one slab, and that one partial (240 of 256 pixels)
+BN_PLAN_SHAPES = [(3, 254, 258, 16), (1, 66, 70, 512), (2, 90, 94, 132), (1, 12, 20, 16)]
+#   (2,48,50,8) f 8       480 slabs from the grid target (512), one chunk
+#   (1,40,44,132) f 4     three chunks (the last one a single quad), 160 slabs from the target (171)
+#   (2,128,132,64) f 2    540 672 quads: the grid of up_gx_kernel is capped
+UP_PLAN_SHAPES = [((2, 48, 50, 8), 8), ((1, 40, 44, 132), 4), ((2, 128, 132, 64), 2)]                # ((N, H, W, C), f)
+
+
+def _bn_regimes():
+    """name -> predicate over (shape, plan): what make_bn_plan, the reduce kernels and the element-wise kernels branch on"""
+    r = OrderedDict()
+    r['slabs cut by the pixels'] = lambda s, p: p['capped']
+    r['slabs from the grid target'] = lambda s, p: not p['capped']
+    r['slabs == 1'] = lambda s, p: p['slabs'] == 1
+    r['slabs == 512'] = lambda s, p: p['slabs'] == 512
+    r['a partial last slab'] = lambda s, p: p['last_slab_pixels'] < p['pixPerSlab']
+    r['chunks == 1'] = lambda s, p: p['chunks'] == 1
+    r['chunks == 2'] = lambda s, p: p['chunks'] == 2
+    r['dead threads (256 % cw != 0)'] = lambda s, p: p['dead_threads'] > 0
+    r['dead threads, slabs from the grid target'] = lambda s, p: p['dead_threads'] > 0 and not p['capped']
+    r['element-wise grid uncapped'] = lambda s, p: not p['ew_capped']
+    r['element-wise grid capped'] = lambda s, p: p['ew_capped']
+    r['element-wise grid capped, total not a multiple of 2048 * 256'] = lambda s, p: p['ew_ragged']
+    return r
+
+
+def _up_regimes():
+    """name -> predicate over ((N, H, W, C, f), plan)"""
+    r = OrderedDict()
+    r['slabs cut by the pixels'] = lambda s, p: p['capped']
+    r['slabs from the grid target'] = lambda s, p: not p['capped']
+    r['chunks == 1'] = lambda s, p: p['chunks'] == 1
+    r['chunks > 1'] = lambda s, p: p['chunks'] > 1
+    r['up_gx grid uncapped'] = lambda s, p: not p['ew_capped']
+    r['up_gx grid capped'] = lambda s, p: p['ew_capped']
+    for f in (2, 4, 8):
+        r['f == %d' % f] = lambda s, p, f=f: p['f'] == f
+        r['f == %d, slabs from the grid target' % f] = lambda s, p, f=f: p['f'] == f and not p['capped']   # one kernel per f
+    return r
+
+
+BN_REGIMES, UP_REGIMES = _bn_regimes(), _up_regimes()
+
+
+def reached(regimes, plans):
+    """names of the regimes some (shape, plan) of the list reaches"""
+    return [name for name, pred in regimes.items() if any(pred(s, p) for s, p in plans)]
+
+
+def reached_bn_regimes(shapes):
+    return reached(BN_REGIMES, [(s, bn_plan(*s)) for s in shapes])
+
+
+def reached_up_regimes(shapes):
+    """``shapes``: (N, H, W, C, f)"""
+    return reached(UP_REGIMES, [(s, up_plan(*s)) for s in shapes])
+
+
+def missing_bn_regimes(shapes):
+    """names of the BatchNorm regimes no (N, H, W, C) of the list reaches"""
+    got = reached_bn_regimes(shapes)
+    return [name for name in BN_REGIMES if name not in got]
+
+
+def missing_up_regimes(shapes):
+    """names of the up-sampling regimes no (N, H, W, C, f) of the list reaches"""
+    got = reached_up_regimes(shapes)
+    return [name for name in UP_REGIMES if name not in got]
+
+
+def gpu_bn_shapes():
+    """every (N, H, W, C) the BatchNorm op tests of tests/test_hip_neck_backward.py run"""
+    return list(BN_SHAPES) + list(BN_PLAN_SHAPES)
+
+
+def gpu_up_shapes():
+    """every (N, H, W, C, f) the up-sampling op tests of tests/test_hip_neck_backward.py run"""
+    return [s + (f,) for s in UP_SHAPES for f in (2, 4, 8)] + [s + (f,) for s, f in UP_PLAN_SHAPES]
+
+
 DEFORM_SHAPES = [(2, 5, 7, 128, 64), (3, 5, 6, 64, 64)]                   # (N, H, W, Cin, Cout)
 IDA = dict(o=64, channels=[64, 128, 256], up_f=[1, 2, 4], N=2, sizes=[(16, 24), (8, 12), (4, 6)])
 DLAUP = dict(startp=2, channels=[64, 128, 256, 512], scales=[1, 2, 4, 8], N=1, sizes=[(16, 16), (8, 8), (4, 4), (2, 2)])
@@ -62,6 +171,37 @@ def ida_nodes(o, channels, up_f, N, sizes):
         (h, w), f = sizes[i], up_f[i]
         calls += [('bn', N, h, w, o), ('up', N, h, w, o, f), ('bn', N, h * f, w * f, o)]
     return calls
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the BatchNorm case of the op tests
+
+def bn_case(shape, residual=False):
+    """fp32 [z, gamma, beta, running_mean, running_var, gy(, res)] (NCHW): z with a channel of mean 100 / std 0.01 (0), a
+    constant channel (1) and a channel whose pre-activations are all negative (2: beta = -30); gamma of both signs"""
+    N, H, W, C = shape
+    z = randn(31, N, C, H, W)
+    z[:, 0] = 100 + 0.01 * z[:, 0]
+    z[:, 1] = 3.0
+    gamma = randn(32, C) * 0.5 + 1.0
+    gamma[3::2] *= -1
+    beta = randn(33, C) * 0.3
+    beta[2] = -30.0
+    rm, rv = randn(34, C) * 0.2, torch.rand(C, generator=torch.Generator().manual_seed(35), dtype=torch.float64) + 0.5
+    rm[0] = 100.0
+    t = [z, gamma, beta, rm, rv, randn(36, N, C, H, W)]
+    if residual:
+        t.append(randn(37, N, C, H, W))
+    return [v.float() for v in t]
+
+
+def bn_free_run(case, dtype, batch, residual=False):
+    """(pre-activation, relu of it) of BatchNorm (+ res) in ``dtype`` with its own mask"""
+    z, gamma, beta, rm, rv = (t.to(dtype) for t in case[:5])
+    pre = F.batch_norm(z, rm.clone(), rv.clone(), gamma, beta, batch, MOMENTUM, EPS)
+    if residual:
+        pre = pre + case[6].to(dtype)
+    return pre, torch.relu(pre)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -214,6 +214,86 @@ def test_the_restated_plans_give_the_librarys_workspace_sizes(lib):
     assert BB.s2_plan(4, 512, 512, 16, 32)['slabs'] == 114 and BB.s2_plan(4, 32, 32, 256, 512)['slabs'] == 2
 
 
+def _production_calls():
+    """the stride-2 (N, H, W, Cin, Cout), BatchNorm (N, H, W, C) and pool (N, H, W, C) calls of a DLA-34 training step at the
+    two shapes of the backbone benchmark"""
+    s2, bn, pool = [], [], []
+    for N, H, W in BB.bench_shapes():
+        for call in BB.dla_units(N, H, W):
+            (s2 if call[0] == 's2' else bn).append(call[1:])
+        for lv in range(2, 6):                                       # the pool in front of every ``Tree`` reads the level below
+            pool.append((N, H >> (lv - 1), W >> (lv - 1), BB.DLA34['channels'][lv - 1]))
+    return sorted(set(s2)), sorted(set(bn)), sorted(set(pool))
+
+
+def test_the_gpu_shapes_reach_every_regime_of_the_plans():
+    """``_backbone_bwd.S2_REGIMES`` / ``POOL_REGIMES`` / ``BN_REGIMES`` against every shape the GPU op tests run; every new shape
+    is there for a regime nothing else reaches; and what a production call reaches, a GPU shape reaches.  2048 * 256, the
+    quad count from which ``ew_grid`` caps the element-wise grids, is not observable through the ABI: ``_neck_bwd.EW_CAP``
+    mirrors it by reading."""
+    s2_all, pool_all = BB.S2_SHAPES + BB.S2_PLAN_SHAPES, BB.POOL_SHAPES + BB.POOL_PLAN_SHAPES
+    assert BB.missing_s2_regimes(s2_all) == []
+    assert BB.missing_pool_regimes(pool_all) == []
+    assert BB.missing_bn_regimes(BB.gpu_bn_shapes()) == []
+    assert set(BB.missing_s2_regimes(BB.S2_SHAPES)) >= {
+        'slabs from cdiv(1024, units)', 'stepsPerWave % 4 == 3', 'a whole idle slab',
+        'nco < 4 in a cout group other than the first', 'Cin % 32 == 16 with more than one channel group',
+        'Cout % 64 != 0 with Cout > 64', 'Wo % 16 == 0 and Ho % 4 == 0'}                           # what the toy shapes left out
+    assert 'grid capped' in BB.missing_pool_regimes(BB.POOL_SHAPES)
+    for i, s in enumerate(BB.S2_PLAN_SHAPES):
+        assert BB.missing_s2_regimes(BB.S2_SHAPES + BB.S2_PLAN_SHAPES[:i] + BB.S2_PLAN_SHAPES[i + 1:]) != [], s
+    s2, bn, pool = _production_calls()
+    assert set(BB.reached_s2_regimes(s2)) <= set(BB.reached_s2_regimes(s2_all))
+    assert set(BB.reached_bn_regimes(bn)) <= set(BB.reached_bn_regimes(BB.gpu_bn_shapes()))
+    assert set(BB.reached_pool_regimes(pool)) <= set(BB.reached_pool_regimes(pool_all))
+    assert {'slabs from cdiv(1024, units)', 'a whole idle wave'} <= set(BB.reached_s2_regimes(s2))   # production is past the toy sizes
+    assert 'element-wise grid capped' in BB.reached_bn_regimes(bn) and 'grid capped' in BB.reached_pool_regimes(pool)
+    # the figures the comments of the shape lists give
+    a, b, c, d = (BB.s2_plan(*s) for s in BB.S2_PLAN_SHAPES)
+    assert (a['gw_units'], a['wanted'], a['maxSlabs'], a['slabs'], a['stepsPerWave'], a['nsteps']) == (36, 29, 38, 29, 11, 1200)
+    assert (a['idle_waves'], a['idle_slabs']) == (6, 1)
+    assert (b['gw_units'], b['slabs'], b['stepsPerWave'], b['cogroups']) == (576, 2, 36, 8)
+    assert (c['cgroups'], c['cogroups'], c['nco_last'], c['slabs']) == (2, 2, 1, 1)
+    assert (d['Wo'], d['Ho'], d['gx_units'], d['stepsPerWave']) == (16, 4, 1, 4)
+    assert BB.pool_plan(*BB.POOL_PLAN_SHAPES[0])['quads'] == 549120 and BB.pool_plan(*BB.POOL_PLAN_SHAPES[0])['ew_ragged']
+
+
+def test_the_restated_plans_give_the_librarys_workspace_sizes_at_the_plan_shapes(lib):
+    keep, p = _ptr()
+    for N, H, W, Cin, Cout in BB.S2_PLAN_SHAPES:
+        d = _s2_desc(p, N, H, W, Cin, Cout)
+        assert lib.ct_conv2d_s2_backward_workspace_bytes(ctypes.byref(d)) == BB.s2_plan(N, H, W, Cin, Cout)['bytes'] > 0, (N, H, W, Cin, Cout)
+        d.ldx, d.ldgx, d.ldgy = Cin + 32, Cin + 20, Cout + 8         # the pitches of the channel-slice test change no plan
+        assert lib.ct_conv2d_s2_backward_workspace_bytes(ctypes.byref(d)) == BB.s2_plan(N, H, W, Cin, Cout)['bytes']
+    for N, H, W, C in BB.BN_PLAN_SHAPES:
+        for flags in (0, 1, 2, 3):
+            d = _bn_desc(p, N, H, W, C, flags=flags)
+            assert lib.ct_bn_act_workspace_bytes(ctypes.byref(d)) == BB.bn_plan(N, H, W, C)['bytes'] > 0, (N, H, W, C)
+
+
+@pytest.mark.parametrize('batch', [True, False], ids=['batch-stats', 'running-stats'])
+@pytest.mark.parametrize('shape', BB.BN_PLAN_SHAPES, ids=str)
+def test_the_float32_reference_stays_inside_the_mask_cap_at_the_plan_shapes(shape, batch):
+    """what tests/test_hip_backbone_backward.py holds the HIP forward's ReLU mask to (``check_mask``: flips only within 64 e32
+    of 0, on at most 0.1 % of the map), held by the float32 CPU run of the same case with its residual"""
+    case = BB.bn_case(shape)
+    (pre64, y64), (pre32, y32) = (BB._neck_bwd.bn_free_run(case, dt, batch, residual=True) for dt in (torch.float64, torch.float32))
+    flipped, near = BB.check_mask(pre32 > 0, pre64, BB.err(y32, y64), str(shape))
+    print('%s: fp32 torch flips %d units, %d of %d within the threshold' % (shape, flipped, near, pre64.numel()))
+
+
+def test_the_capped_pool_case_is_full_of_ties():
+    """the tie rule at the shape whose grid is capped: torch's backward equals the explicit first-maximum sums bit for bit, and
+    half of the windows tie"""
+    N, H, W, C = BB.POOL_PLAN_SHAPES[0]
+    x = BB.tie_input(41, N, C, H, W)
+    assert BB.tie_fraction(x) >= 0.3
+    gy = BB.randn(42, N, C, H // 2, W // 2).float()
+    xt = x.clone().requires_grad_()
+    gx, = torch.autograd.grad(F.max_pool2d(xt, 2, 2), xt, gy)
+    assert torch.equal(BB.pool_backward_formula(x, gy), gx)
+
+
 def test_module_names_shapes_and_initialisation():
     from centertrack_amd import dla_base
     m = dla_base.dla34(pretrained=False, opt=BB.Opt())

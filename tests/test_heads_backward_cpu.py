@@ -156,6 +156,50 @@ def test_the_restated_plans_give_the_librarys_workspace_sizes(lib):
     assert tail[g]['slabs'] == 16
 
 
+def test_the_gpu_cases_reach_every_regime_of_the_tail_plan(lib):
+    """``_heads_bwd.TAIL_REGIMES`` against every case the GPU tests run through ct_heads_tail_backward; the new case is there for
+    regimes nothing else reaches; what production reaches -- the MOT and nuScenes heads at batch 1 and 4 on 512 x 512 and
+    800 x 448 -- a GPU case reaches; and the library's workspace query equals the restated plan at the new case"""
+    keep, p = _ptr()
+    assert HB.missing_tail_regimes(HB.tail_cases()) == []
+    assert set(HB.missing_tail_regimes(HB.SHAPES)) == {
+        'slabs from the grid target', 'pixPerSlab >= 128', 'a last slab of more than one tile whose last tile is ragged'}
+    prod = [((n, h, w), hd) for n in (1, 4) for h, w in ((128, 128), (112, 200)) for hd in (HB.MOT, HB.NUSC)]
+    assert set(HB.reached_tail_regimes(prod)) <= set(HB.reached_tail_regimes(HB.tail_cases()))
+    assert 'pixPerSlab >= 128' in HB.reached_tail_regimes(prod)                       # production is past one tile per slab
+    assert HB.tail_plan(4, 128, 128, HB.HC, tuple(HB.MOT.values()))['pixPerSlab'] == 128
+    for (N, H, W), heads in prod + [HB.TAIL_CASE]:
+        cs = tuple(heads.values())
+        t, arr = _tail_desc(p, cs, N, H, W)
+        assert lib.ct_heads_tail_backward_workspace_bytes(ctypes.byref(t)) == HB.tail_plan(N, H, W, HB.HC, cs)['bytes'] > 0
+    (N, H, W), heads = HB.TAIL_CASE
+    plan = HB.tail_plan(N, H, W, HB.HC, tuple(heads.values()))
+    assert (plan['wanted'], plan['maxSlabs'], plan['pixPerSlab'], plan['slabs'], plan['last_slab_pixels']) == (64, 66, 128, 33, 86)
+    assert len(heads) == 16 and H * W == 2091 and plan['passes'] == [2] * 16
+
+
+def test_the_tail_truth_is_autograd():
+    """``_heads_bwd.tail_truth`` (explicit sums over a hidden map that is given) against torch autograd of relu -> conv1x1 per
+    head behind a 3x3 convolution, float64, on a small map"""
+    case = ((2, 5, 7), HB.OrderedDict([('a', 20), ('b', 3)]))
+    fx = HB.tail_fixture(case)
+    want = HB.tail_truth(fx, torch.float64)
+    nh = len(case[1])
+    # a pre-activation whose ReLU is ``mid``: mid where it is positive, -1 elsewhere
+    pre = torch.where(fx['mid'] > 0, fx['mid'], -torch.ones_like(fx['mid'])).double().requires_grad_()
+    w2 = [fx['w2'][h].double().requires_grad_() for h in case[1]]
+    b2 = [torch.zeros(c, dtype=torch.float64, requires_grad=True) for c in case[1].values()]
+    mid = torch.relu(pre)
+    tot = sum((HB.F.conv2d(mid[:, HB.HC * j:HB.HC * (j + 1)], w2[j], b2[j]) * fx['gout'][h].double()).sum() for j, h in enumerate(case[1]))
+    g = torch.autograd.grad(tot, [pre] + w2 + b2)
+    assert HB.err(want['gmid'], g[0]) < 1e-14
+    for j, h in enumerate(case[1]):
+        assert HB.err(want['w2'][h], g[1 + j]) < 1e-14 and HB.err(want['b2'][h], g[1 + nh + j]) < 1e-14
+    x = torch.zeros(2, HB.CIN, 5, 7, dtype=torch.float64, requires_grad=True)
+    gx, = torch.autograd.grad(HB.F.conv2d(x, fx['w0'].double(), padding=1), x, want['gmid'])
+    assert HB.err(want['x'], gx) < 1e-14
+
+
 def test_fused_heads_names_shapes_and_initialisation():
     from centertrack_amd import heads as HD, weights
     from centertrack_amd._lib import CTError

@@ -15,6 +15,11 @@ map (tests/test_backbone_backward_cpu.py holds the float32 reference itself to t
 convolutions have no bias, so under batch statistics no parameter gradient is 0 in exact arithmetic; a parameter nothing
 reads (the ``project`` of a two-level ``Tree``, whose result the reference drops) gets no gradient at all, here and there.
 
+The op tests run twice: at toy shapes (``S2_SHAPES``, ``BN_SHAPES``, ``POOL_SHAPES``), where every slab count sits at its pixel
+limit, and at ``S2_PLAN_SHAPES`` / ``BN_PLAN_SHAPES`` / ``POOL_PLAN_SHAPES``, the smallest shapes that reach what production training
+and the API reach beyond that (``_backbone_bwd.S2_REGIMES`` / ``POOL_REGIMES``, ``_neck_bwd.BN_REGIMES``;
+tests/test_backbone_backward_cpu.py holds the lists against them).
+
 Measured on an MI355X (largest error / its bound per group): see DESIGN.md section 13."""
 import pytest
 import torch
@@ -46,18 +51,26 @@ def untouched(v):
     return bool((v.buf.cpu()[..., rest] == 7.0).all())
 
 
+def sentinel_view(N, H, W, C, dev, c0=4, tail=4):
+    """a caller-owned output view, channels c0 .. c0 + C of a wider buffer: NaN where the kernel has to write, 7 in the padding"""
+    from centertrack_amd import ops
+    buf = torch.full((N, H, W, c0 + C + tail), 7.0, device=dev)
+    buf[..., c0:c0 + C] = float('nan')
+    return ops.View(buf, c0, C)
+
+
+def poison(dev, *numels):
+    """An output the wrapper allocates itself comes from torch's caching allocator, which may hand back the block an earlier
+    run of the same case wrote.  Blocks of these sizes are filled with NaN and freed first (stream-ordered), so that an
+    element the kernel skips is seen by the comparison that follows."""
+    blocks = [torch.full((n,), float('nan'), device=dev) for n in numels]
+    del blocks
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the stride-2 convolution
 
-def s2_case(shape):
-    N, H, W, Cin, Cout = shape
-    x, w = BB.randn(11, N, Cin, H, W).float(), (BB.randn(12, Cout, Cin, 3, 3) * (9 * Cin) ** -0.5).float()
-    gy = BB.randn(13, N, Cout, H // 2, W // 2).float()
-    ref = {}
-    for dt in (torch.float64, torch.float32):
-        xt, wt = x.to(dt).requires_grad_(), w.to(dt).requires_grad_()
-        ref[dt] = torch.autograd.grad(F.conv2d(xt, wt, None, 2, 1), (xt, wt), gy.to(dt))
-    return x, w, gy, ref
+s2_case = BB.s2_case
 
 
 @pytest.mark.parametrize('shape', BB.S2_SHAPES, ids=str)
@@ -99,24 +112,55 @@ def test_conv_s2_backward_on_channel_slices(device):
     rep.check()
 
 
+@pytest.mark.parametrize('shape', BB.S2_PLAN_SHAPES, ids=str)
+def test_conv_s2_backward_at_plan_shapes(device, shape):
+    """``test_conv_s2_backward`` at the plans and channel edges ``_backbone_bwd.S2_PLAN_SHAPES`` names: a slab count from the
+    grid target with idle waves and an idle slab, 36 steps per wave, Cin 48 / Cout 80, one tile with its halo outside the map;
+    gx goes into a caller-owned view pre-filled with NaN"""
+    from centertrack_amd import ops
+    N, H, W, Cin, Cout = shape
+    x, w, gy, ref = s2_case(shape)
+    xv, gyv, wd = nhwc_view(x, device), nhwc_view(gy, device), w.to(device)
+    nw = Cout * Cin * 9
+
+    def run(**kw):
+        gxv = sentinel_view(N, H, W, Cin, device) if kw.get('need_x', True) else None
+        poison(device, nw, nw)                                            # the packed weight and gw
+        gx, gw = ops.conv_s2_backward(xv, gyv, wd, gx=gxv, **kw)
+        assert gx is gxv and (gxv is None or untouched(gxv))
+        return gx, gw
+    gx, gw = run()
+    rep = Report('conv s2 plan %s' % (shape,))
+    rep.add('gx', back(gx), ref[torch.float64][0], ref[torch.float32][0], 4 * Cout)
+    rep.add('gw', gw, ref[torch.float64][1], ref[torch.float32][1], N * (H // 2) * (W // 2))
+    gx1, none = run(need_w=False)
+    assert none is None and torch.equal(gx1.buf, gx.buf)
+    none, gw1 = run(need_x=False)
+    assert none is None and torch.equal(gw1, gw)
+    gx2, gw2 = run()
+    assert torch.equal(gx2.buf, gx.buf) and torch.equal(gw2, gw)
+    rep.check()
+
+
+def test_conv_s2_backward_on_channel_slices_at_a_plan_shape(device):
+    """the 29-slab case once dense and once with x, gy and gx as channel slices of wider buffers: the pitch changes no bit"""
+    from centertrack_amd import ops
+    shape = BB.S2_PLAN_SHAPES[0]
+    N, H, W, Cin, Cout = shape
+    assert BB.s2_plan(*shape)['idle_slabs'] == 1
+    x, w, gy, ref = s2_case(shape)
+    wd = w.to(device)
+    dense = ops.conv_s2_backward(nhwc_view(x, device), nhwc_view(gy, device), wd)
+    xv, gyv, gxv = nhwc_view(x, device, Cin + 32, 16), nhwc_view(gy, device, Cout + 8, 4), sentinel_view(N, H, W, Cin, device, 8, 12)
+    gx, gw = ops.conv_s2_backward(xv, gyv, wd, gx=gxv)
+    assert gx is gxv and untouched(gxv) and untouched(xv) and untouched(gyv)
+    assert torch.equal(back(gx), back(dense[0])) and torch.equal(gw, dense[1])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # BatchNorm (+ residual) (+ ReLU)
 
-def bn_case(shape):
-    """tests/test_hip_neck_backward.py's case -- z with a channel of mean 100 / std 0.01 (0), a constant channel (1) and a
-    channel whose pre-activations are all negative (2: beta = -30); gamma of both signs -- plus a residual"""
-    N, H, W, C = shape
-    z = BB.randn(31, N, C, H, W)
-    z[:, 0] = 100 + 0.01 * z[:, 0]
-    z[:, 1] = 3.0
-    gamma = BB.randn(32, C) * 0.5 + 1.0
-    gamma[3::2] *= -1
-    beta = BB.randn(33, C) * 0.3
-    beta[2] = -30.0
-    rm, rv = BB.randn(34, C) * 0.2, torch.rand(C, generator=torch.Generator().manual_seed(35), dtype=torch.float64) + 0.5
-    rm[0] = 100.0
-    gy, res = BB.randn(36, N, C, H, W), BB.randn(37, N, C, H, W)
-    return [t.float() for t in (z, gamma, beta, rm, rv, gy, res)]
+bn_case = BB.bn_case
 
 
 def bn_reference(case, dtype, batch, relu, residual, mask=None):
@@ -190,16 +234,98 @@ def test_bn_act_ops(device, shape, relu, residual, batch):
     rep.check()
 
 
+PLAN_MODES = {'relu-res': (True, True, True), 'relu': (True, False, True), 'linear-res': (False, True, True),
+              'relu-res-running': (True, True, False)}                    # (relu, residual, batch statistics)
+
+
+@pytest.mark.parametrize('mode', list(PLAN_MODES))
+@pytest.mark.parametrize('shape', BB.BN_PLAN_SHAPES, ids=str)
+def test_bn_act_ops_at_plan_shapes(device, shape, mode):
+    """``test_bn_act_ops`` where the slab count comes from the grid target and the element-wise grids are capped at 2048
+    workgroups (``_neck_bwd.BN_PLAN_SHAPES``); y goes into a caller-owned view pre-filled with NaN"""
+    from centertrack_amd import ops
+    relu, residual, batch = PLAN_MODES[mode]
+    N, H, W, C = shape
+    P = N * H * W
+    case = bn_case(shape)
+    z, gamma, beta, rm, rv, gy, res = case
+    zv, gyv = nhwc_view(z, device), nhwc_view(gy, device)
+    rv_ = nhwc_view(res, device) if residual else None
+    g, b = gamma.to(device), beta.to(device)
+    rep = Report('bn-act plan %s %s' % (shape, mode))
+    if batch:
+        mean, var, invstd = ops.bn_stats(zv, BB.EPS)
+    else:
+        mean, var = rm.to(device), rv.to(device)
+        invstd = torch.rsqrt(var + BB.EPS)
+
+    def run(**need):
+        out = sentinel_view(N, H, W, C, device)
+        y = ops.bn_act_apply(zv, mean, invstd, g, b, res=rv_, relu=relu, out=out)
+        assert y is out and untouched(out)
+        poison(device, P * C, P * C)                                      # gz and gres
+        return (y,) + ops.bn_act_backward(zv, gyv, mean, invstd, g, b, batch, res=rv_, relu=relu, need_res=residual, **need)
+    y, gz, gr, gg, gb = run()
+    yh = back(y)
+    mask = yh > 0
+    free64, free32 = (bn_reference(case, dt, batch, relu, residual) for dt in (torch.float64, torch.float32))
+    t64, t32 = (bn_reference(case, dt, batch, relu, residual, mask) for dt in (torch.float64, torch.float32))
+    if relu:
+        flipped, near = BB.check_mask(mask, free64['pre'], err(free32['y'], free64['y']), rep.title)
+        print('%s: %d ReLU units flipped, %d within the threshold, of %d' % (rep.title, flipped, near, mask.numel()))
+    rep.add('y', yh, free64['y'], free32['y'], P)
+    rep.add('gz', back(gz), t64['gz'], t32['gz'], P)
+    rep.add('ggamma', gg, t64['gg'], t32['gg'], P)
+    rep.add('gbeta', gb, t64['gb'], t32['gb'], P)
+    if residual:
+        rep.add('gres', back(gr), t64['gr'], t32['gr'], P)
+        assert torch.equal(back(gr), torch.where(mask, gy, torch.zeros_like(gy)) if relu else gy)   # a pure selection
+    else:
+        assert gr is None
+    again = run()
+    for u, v in zip((y, gz, gr, gg, gb), again):
+        assert u is None and v is None or torch.equal(getattr(u, 'buf', u), getattr(v, 'buf', v))
+    frozen = run(need_gamma=False, need_beta=False)
+    assert frozen[3] is None and frozen[4] is None and torch.equal(frozen[1].buf, gz.buf)
+    assert gr is None or torch.equal(frozen[2].buf, gr.buf)
+    only = run(need_z=False, need_gamma=False)
+    assert only[1] is None and only[3] is None and torch.equal(only[4], gb) and (gr is None or torch.equal(only[2].buf, gr.buf))
+    if relu and not residual:                           # the neck's kernels, bit for bit
+        y0 = ops.bn_relu_apply(zv, mean, invstd, g, b)
+        gz0, gg0, gb0 = ops.bn_relu_backward(zv, gyv, mean, invstd, g, b, batch)
+        assert torch.equal(y0.buf, y.buf[..., y.c0:y.c0 + C]) and torch.equal(gz0.buf, gz.buf)
+        assert torch.equal(gg0, gg) and torch.equal(gb0, gb)
+    rep.check()
+
+
+def test_bn_act_ops_on_channel_slices_at_the_capped_shape(device):
+    """the 512-slab, capped-grid case with a residual once dense and once as channel slices of wider buffers: the pitch
+    changes no bit"""
+    from centertrack_amd import ops
+    shape = BB.BN_PLAN_SHAPES[0]
+    N, H, W, C = shape
+    assert BB.bn_plan(*shape)['slabs'] == 512 and BB.bn_plan(*shape)['ew_ragged']
+    z, gamma, beta, rm, rv, gy, res = bn_case(shape)
+    g, b = gamma.to(device), beta.to(device)
+
+    def run(zv, gyv, rsv, out):
+        mean, var, invstd = ops.bn_stats(zv, BB.EPS)
+        y = ops.bn_act_apply(zv, mean, invstd, g, b, res=rsv, relu=True, out=out)
+        gz, gr, gg, gb = ops.bn_act_backward(zv, gyv, mean, invstd, g, b, True, res=rsv, relu=True, need_res=True)
+        return [back(y), back(gz), back(gr), gg, gb]
+    dense = run(nhwc_view(z, device), nhwc_view(gy, device), nhwc_view(res, device), None)
+    views = nhwc_view(z, device, 24, 4), nhwc_view(gy, device, 20, 0), nhwc_view(res, device, 32, 12)
+    out = sentinel_view(N, H, W, C, device, 8, 4)
+    sliced = run(*views, out)
+    assert untouched(out) and all(untouched(v) for v in views)
+    for name, u, v in zip(('y', 'gz', 'gres', 'ggamma', 'gbeta'), dense, sliced):
+        assert torch.equal(u, v), name
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # max-pool backward
 
-def tie_input(seed, N, C, H, W):
-    """a post-ReLU map: most windows all zero, one of equal positive values, -0.0 in front of and behind a 0"""
-    x = torch.relu(BB.randn(seed, N, C, H, W) - 1.0)
-    x[:, :, 0:2, 0:2] = 0.75
-    x[:, 0::2, -2, -2] = -0.0
-    x[:, 1::2, -1, -1] = -0.0
-    return x.float()
+tie_input = BB.tie_input
 
 
 @pytest.mark.parametrize('with_add', [False, True], ids=['plain', 'add'])
@@ -230,6 +356,30 @@ def test_maxpool_backward(device, shape, with_add):
         y = dla_base._MaxPoolFunction.apply(xd)
     g, = torch.autograd.grad(y, xd, gyv.buf[..., gyv.c0:gyv.c0 + C].contiguous())
     assert torch.equal(g.permute(0, 3, 1, 2).cpu(), plain)
+
+
+@pytest.mark.parametrize('with_add', [False, True], ids=['plain', 'add'])
+@pytest.mark.parametrize('shape', BB.POOL_PLAN_SHAPES, ids=str)
+def test_maxpool_backward_with_a_capped_grid(device, shape, with_add):
+    """549 120 windows x channel quads on 2048 workgroups: the grid-stride loop runs a second, ragged round.  torch's result
+    bit for bit, into a caller-owned view pre-filled with NaN"""
+    from centertrack_amd import ops
+    N, H, W, C = shape
+    assert BB.pool_plan(*shape)['ew_ragged']
+    x = tie_input(41, N, C, H, W)
+    assert BB.tie_fraction(x) >= 0.3
+    gy, add = BB.randn(42, N, C, H // 2, W // 2).float(), BB.randn(43, N, C, H, W).float()
+    xt = x.clone().requires_grad_()
+    plain, = torch.autograd.grad(F.max_pool2d(xt, 2, 2), xt, gy)
+    want = plain + add if with_add else plain                            # one fp32 addition per element, here and there
+    xv, gyv = nhwc_view(x, device), nhwc_view(gy, device, C + 4, 4)
+    addv = nhwc_view(add, device, C + 4, 0) if with_add else None
+    out = sentinel_view(N, H, W, C, device)
+    gx = ops.maxpool2x2_backward(xv, gyv, add=addv, out=out)
+    assert gx is out and untouched(out) and untouched(gyv)
+    assert torch.equal(back(gx), want)                                   # bitwise: a pure selection
+    out2 = sentinel_view(N, H, W, C, device, 0, 0)
+    assert torch.equal(ops.maxpool2x2_backward(xv, gyv, add=addv, out=out2).buf, out.buf[..., 4:4 + C])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,8 @@ K = c for gmid.  The fixture's hidden pre-activation is exact in fp32 (tests/_he
 and of the truth are the same set: the HIP hidden map must equal torch's bit for bit.
 
 Shapes: ``_heads_bwd.SHAPES``; its comment names the branch of the two host plans each one reaches, and
-tests/test_heads_backward_cpu.py asserts that."""
+tests/test_heads_backward_cpu.py asserts that; ``_heads_bwd.TAIL_CASE`` runs the tail alone at two tiles per slab, the plan of
+training at batch 4, on a hidden map that is built directly (``_heads_bwd.TAIL_REGIMES`` names what the cases reach)."""
 from collections import OrderedDict
 
 import pytest
@@ -69,6 +70,65 @@ def test_gradients_against_float64_autograd(device, case):
     # torch's ReLU convention: no gradient where the hidden value is exactly 0 (the fixture has such units)
     dead = t64['mid'] == 0
     assert bool((t64['pre'] == 0).any()) and float(res['gmid'].to_nchw().cpu()[dead].abs().max()) == 0.0
+    assert not fails, fails
+
+
+def test_the_tail_at_two_tiles_per_slab(device):
+    """``_heads_bwd.TAIL_CASE``: ``pixPerSlab`` 128, so the tile loop of heads_tail_weight_kernel runs twice -- ``g`` re-staged,
+    ``bsum`` carried -- with a last slab of a full and a ragged tile and a tile across the image border.  Once with only
+    ``w2`` / ``b2`` needed (the weight part alone), once with ``x`` needed as well (the hidden gradient into a caller-owned view
+    pre-filled with NaN, 7 in its pitch padding), against the float64 sums over the hidden map itself; K = N*H*W for gw2 and
+    gb2, c for gmid, 9 * hc * nheads for gx.  Two runs are bitwise equal, and leaving ``x`` out changes no bit of gw2 / gb2."""
+    from centertrack_amd import ops
+    case = HB.TAIL_CASE
+    (N, H, W), heads = case
+    plan = HB.tail_plan(N, H, W, HB.HC, tuple(heads.values()))
+    assert (plan['pixPerSlab'], plan['slabs'], plan['last_slab_pixels']) == (128, 33, 86) and (H * W) % 64 != 0
+    fx = HB.tail_fixture(case)
+    t64, t32 = HB.tail_truth(fx, torch.float64), HB.tail_truth(fx, torch.float32)
+    C = HB.HC * len(heads)
+    mid = ops.View(fx['mid'].permute(0, 2, 3, 1).contiguous().to(device))
+    w0 = fx['w0'].to(device)
+    w2s = OrderedDict((h, fx['w2'][h].to(device)) for h in heads)
+    gouts = OrderedDict((h, fx['gout'][h].to(device)) for h in heads)
+    tag = '%dx%dx%d-%d heads of 20' % (N, H, W, len(heads))
+    fails = []
+
+    def flat(r):
+        return [r['w2'][h] for h in heads] + [r['b2'][h] for h in heads]
+
+    def poison():
+        """gw2 / gb2 come from torch's caching allocator, which may hand back what an earlier run wrote: blocks of their sizes
+        are filled with NaN and freed first, so that an element the reduce kernel skips is seen"""
+        blocks = [torch.full((n,), float('nan'), device=device) for c in heads.values() for n in (c * HB.HC, c)]
+        del blocks
+    poison()
+    tail = ops.heads_backward(None, mid, gouts, w0, w2s, {'w2': True, 'b2': True})
+    assert tail['gmid'] is None and tail['x'] is None and tail['w0'] is None
+    for h in heads:
+        _judge(fails, tag, 'gw2 ' + h, tail['w2'][h], t64['w2'][h], t32['w2'][h], N * H * W)
+        _judge(fails, tag, 'gb2 ' + h, tail['b2'][h], t64['b2'][h], t32['b2'][h], N * H * W)
+
+    def full():
+        gbuf = torch.full((N, H, W, C + 16), 7.0, device=device)
+        gbuf[..., :C] = float('nan')
+        poison()
+        r = ops.heads_backward(None, mid, gouts, w0, w2s, {'x': True, 'w2': True, 'b2': True}, gmid=ops.View(gbuf, 0, C))
+        assert r['gmid'].buf is gbuf and bool((gbuf[..., C:] == 7.0).all())
+        return r
+    res = full()
+    for a, b in zip(flat(res), flat(tail)):
+        assert torch.equal(a, b)                                         # the hidden gradient changes no bit of the weight part
+    gm = res['gmid'].to_nchw().cpu()
+    for j, (h, c) in enumerate(heads.items()):
+        sl = slice(HB.HC * j, HB.HC * (j + 1))
+        _judge(fails, tag, 'gmid ' + h, gm[:, sl], t64['gmid'][:, sl], t32['gmid'][:, sl], c)
+    dead = fx['mid'] == 0
+    assert 0.4 < float(dead.double().mean()) < 0.6 and float(gm[dead].abs().max()) == 0.0
+    _judge(fails, tag, 'gx', res['x'].to_nchw(), t64['x'], t32['x'], 9 * HB.HC * len(heads))
+    again = full()
+    for a, b in zip(flat(res) + [res['gmid'].buf, res['x'].buf], flat(again) + [again['gmid'].buf, again['x'].buf]):
+        assert torch.equal(a, b)
     assert not fails, fails
 
 

@@ -4,7 +4,12 @@ the CPU of the restated reference construction (tests/_neck_bwd.py).  Error meas
 e32 the float32 CPU run of the same construction.  K = N*H*W for the BatchNorm gradients, the up-sampling weight gradient and
 every weight and bias gradient, 4 f^2 for the up-sampling input gradient, ``_dcn_bwd.terms`` for what the DCN produces
 (36 Cout for an input gradient), and 9 Cin -- the terms of one output element -- for a forward output.  Gradient truths take
-the ReLU mask from the HIP forward's own output; a separate assertion holds that mask (``_neck_bwd.check_mask``)."""
+the ReLU mask from the HIP forward's own output; a separate assertion holds that mask (``_neck_bwd.check_mask``).
+
+The op tests run twice: at toy shapes (``BN_SHAPES``, ``UP_SHAPES``), where every slab count sits at its pixel limit, and at
+``BN_PLAN_SHAPES`` / ``UP_PLAN_SHAPES``, the smallest shapes that reach what production training reaches -- a slab count from the
+grid target, an element-wise grid capped at 2048 workgroups (``_neck_bwd.BN_REGIMES`` / ``UP_REGIMES``;
+tests/test_neck_backward_cpu.py holds the lists against them)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -53,21 +58,7 @@ def back(v):
 # ---------------------------------------------------------------------------------------------------------------------
 # BatchNorm ops
 
-def bn_case(shape):
-    """z with a channel of mean 100 / std 0.01 (0), a constant channel (1) and a channel whose pre-activations are all
-    negative (2: beta = -30); gamma of both signs"""
-    N, H, W, C = shape
-    z = NB.randn(31, N, C, H, W)
-    z[:, 0] = 100 + 0.01 * z[:, 0]
-    z[:, 1] = 3.0
-    gamma = NB.randn(32, C) * 0.5 + 1.0
-    gamma[3::2] *= -1
-    beta = NB.randn(33, C) * 0.3
-    beta[2] = -30.0
-    rm, rv = NB.randn(34, C) * 0.2, torch.rand(C, generator=torch.Generator().manual_seed(35), dtype=torch.float64) + 0.5
-    rm[0] = 100.0
-    gy = NB.randn(36, N, C, H, W)
-    return [t.float() for t in (z, gamma, beta, rm, rv, gy)]
+bn_case = NB.bn_case
 
 
 def bn_reference(case, dtype, batch, mask=None):
@@ -151,6 +142,142 @@ def test_bn_running_statistics_after_two_training_calls(device, shape):
     rep.add('running_mean', bn.running_mean, ref[torch.float64][0], ref[torch.float32][0], P)
     rep.add('running_var', bn.running_var, ref[torch.float64][1], ref[torch.float32][1], P)
     assert int(bn.num_batches_tracked) == 2
+    rep.check()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the launch plans production training reaches (``_neck_bwd.BN_PLAN_SHAPES`` / ``UP_PLAN_SHAPES`` name the regime of each shape)
+
+def sentinel_view(N, H, W, C, dev, c0=4, tail=4):
+    """a caller-owned output view, channels c0 .. c0 + C of a wider buffer: NaN where the kernel has to write, 7 in the padding"""
+    from centertrack_amd import ops
+    buf = torch.full((N, H, W, c0 + C + tail), 7.0, device=dev)
+    buf[..., c0:c0 + C] = float('nan')
+    return ops.View(buf, c0, C)
+
+
+def untouched(v):
+    """the channels of the buffer outside the view still hold the fill value"""
+    rest = torch.ones(v.ld, dtype=torch.bool)
+    rest[v.c0:v.c0 + v.C] = False
+    return bool((v.buf[..., rest.to(v.buf.device)] == 7.0).all())
+
+
+def poison(dev, *numels):
+    """An output the wrapper allocates itself comes from torch's caching allocator, which may hand back the block an earlier
+    run of the same case wrote.  Blocks of these sizes are filled with NaN and freed first (stream-ordered), so that an
+    element the kernel skips is seen by the comparison that follows."""
+    blocks = [torch.full((n,), float('nan'), device=dev) for n in numels]
+    del blocks
+
+
+@pytest.mark.parametrize('batch', [True, False], ids=['batch-stats', 'running-stats'])
+@pytest.mark.parametrize('shape', NB.BN_PLAN_SHAPES, ids=str)
+def test_bn_ops_at_plan_shapes(device, shape, batch):
+    """``test_bn_ops`` where the slab count comes from the grid target and the element-wise grid is capped at 2048
+    workgroups; y goes into a caller-owned view pre-filled with NaN.  Under batch statistics ``y`` at 1x66x70x512 and 1x12x20x16 sits
+    at 0.97 / 0.95 of its bound (measured 3.15e-5 / 3.24e-5 and 2.46e-5 / 2.58e-5): the mean-100 channel, where a = gamma * invstd
+    = 91 multiplies the rounding of the fp32 mean (3.1e-6, 1.2e-6) and nothing else is left"""
+    from centertrack_amd import ops
+    N, H, W, C = shape
+    P = N * H * W
+    case = bn_case(shape)
+    z, gamma, beta, rm, rv, gy = case
+    zv, gyv = nhwc_view(z, device), nhwc_view(gy, device)
+    g, b = gamma.to(device), beta.to(device)
+    rep = Report('bn plan %s %s' % (shape, 'batch' if batch else 'running'))
+
+    def run(need_gamma=True, need_beta=True):
+        if batch:
+            mean, var, invstd = ops.bn_stats(zv, NB.EPS)
+        else:
+            mean, var = rm.to(device), rv.to(device)
+            invstd = torch.rsqrt(var + NB.EPS)
+        out = sentinel_view(N, H, W, C, device)
+        y = ops.bn_relu_apply(zv, mean, invstd, g, b, out=out)
+        assert y is out and untouched(out)
+        poison(device, P * C)
+        gz, gg, gb = ops.bn_relu_backward(zv, gyv, mean, invstd, g, b, batch, need_gamma=need_gamma, need_beta=need_beta)
+        return mean, var, y, gz, gg, gb
+    mean, var, y, gz, gg, gb = run()
+    yh = back(y)
+    mask = yh > 0
+    free64, free32 = bn_reference(case, torch.float64, batch), bn_reference(case, torch.float32, batch)
+    t64, t32 = bn_reference(case, torch.float64, batch, mask), bn_reference(case, torch.float32, batch, mask)
+    flipped, near = NB.check_mask(mask, free64['pre'], err(free32['y'], free64['y']), rep.title)
+    print('%s: %d ReLU units flipped, %d within the threshold, of %d' % (rep.title, flipped, near, mask.numel()))
+    assert not bool(mask[:, 2].any()) and bool((free64['pre'][:, 2] < 0).all())          # the all-negative channel
+    if batch:
+        rep.add('mean', mean, t64['mean'], t32['mean'], P)
+        rep.add('var', var, t64['var'], t32['var'], P)
+        assert float(var[1]) == 0.0                                                      # the constant channel
+    rep.add('y', yh, free64['y'], free32['y'], P)
+    rep.add('gz', back(gz), t64['gz'], t32['gz'], P)
+    rep.add('ggamma', gg, t64['gg'], t32['gg'], P)
+    rep.add('gbeta', gb, t64['gb'], t32['gb'], P)
+    again = run()
+    for u, v in zip((mean, var, y.buf, gz.buf, gg, gb), (again[0], again[1], again[2].buf, again[3].buf, again[4], again[5])):
+        assert torch.equal(u, v)
+    frozen = run(need_gamma=False, need_beta=False)
+    assert frozen[4] is None and frozen[5] is None and torch.equal(frozen[3].buf, gz.buf)
+    only_beta = run(need_gamma=False)
+    assert only_beta[4] is None and torch.equal(only_beta[5], gb) and torch.equal(only_beta[3].buf, gz.buf)
+    rep.check()
+
+
+def test_bn_ops_on_channel_slices_at_the_capped_shape(device):
+    """the 512-slab, capped-grid case once dense and once as channel slices of wider buffers: the pitch changes no bit"""
+    from centertrack_amd import ops
+    shape = NB.BN_PLAN_SHAPES[0]
+    N, H, W, C = shape
+    assert NB.bn_plan(*shape)['slabs'] == 512 and NB.bn_plan(*shape)['ew_ragged']
+    z, gamma, beta, rm, rv, gy = bn_case(shape)
+    g, b = gamma.to(device), beta.to(device)
+
+    def run(zv, gyv, out):
+        mean, var, invstd = ops.bn_stats(zv, NB.EPS)
+        y = ops.bn_relu_apply(zv, mean, invstd, g, b, out=out)
+        gz, gg, gb = ops.bn_relu_backward(zv, gyv, mean, invstd, g, b, True)
+        return [mean, var, back(y), back(gz), gg, gb]
+    dense = run(nhwc_view(z, device), nhwc_view(gy, device), None)
+    zv, gyv, out = nhwc_view(z, device, 24, 4), nhwc_view(gy, device, 20, 0), sentinel_view(N, H, W, C, device, 8, 4)
+    sliced = run(zv, gyv, out)
+    assert untouched(zv) and untouched(gyv) and untouched(out)
+    for name, u, v in zip(('mean', 'var', 'y', 'gz', 'ggamma', 'gbeta'), dense, sliced):
+        assert torch.equal(u, v), name
+
+
+@pytest.mark.parametrize('case', NB.UP_PLAN_SHAPES, ids=str)
+def test_upsample_add_backward_at_plan_shapes(device, case):
+    """``test_upsample_add_backward`` where the slab count comes from the grid target (one kernel per f) and, at f = 2, the
+    grid of the input gradient is capped at 2048 workgroups"""
+    from centertrack_amd import ops
+    shape, f = case
+    N, H, W, C = shape
+    x, w = NB.randn(51, N, C, H, W).float(), (NB.randn(52, C, 1, 2 * f, 2 * f) * 0.5 / f).float()
+    skip, gy = NB.randn(53, N, C, H * f, W * f).float(), NB.randn(54, N, C, H * f, W * f).float()
+    xv, gyv = nhwc_view(x, device), nhwc_view(gy, device, C + 4, 0)
+    wd = w.to(device)
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        t = [v.to(dt).clone().requires_grad_() for v in (x, w, skip)]
+        ref[dt] = torch.autograd.grad(NB.upsample_add(t[0], t[1], f, t[2]), t[:2], gy.to(dt))
+    rep = Report('up plan %s f=%d' % (shape, f))
+
+    def run(**need):
+        poison(device, N * H * W * C)
+        return ops.upsample_add_backward(xv if need.get('need_w', True) else None, wd, f, gyv, **need)
+    gx, gw, gs = run()
+    assert gs is gyv
+    rep.add('gx', back(gx), ref[torch.float64][0], ref[torch.float32][0], 4 * f * f)
+    rep.add('gw', gw, ref[torch.float64][1], ref[torch.float32][1], N * H * W)
+    gx2, gw2, _ = run()
+    assert torch.equal(gx2.buf, gx.buf) and torch.equal(gw2, gw)
+    gx3, none, _ = run(need_w=False)
+    assert none is None and torch.equal(gx3.buf, gx.buf)
+    none, gw3, _ = run(need_x=False)
+    assert none is None and torch.equal(gw3, gw)
+    assert untouched(gyv)
     rep.check()
 
 

@@ -195,6 +195,72 @@ def test_the_restated_plans_give_the_librarys_workspace_sizes(lib):
     assert [(v['chunks'], v['slabs']) for v in u] == [(1, 9), (1, 9), (3, 1)]
 
 
+def _production_calls():
+    """the BatchNorm (N, H, W, C) and up-sampling (N, H, W, C, f) calls of the two ``IDAUp`` of the neck benchmark, batch 1 and 4"""
+    bn, up = [], []
+    for _, b, o, ch, uf, sizes in NB.bench_shapes():
+        for call in NB.ida_nodes(o, ch, uf, b, sizes):
+            (bn if call[0] == 'bn' else up).append(call[1:])
+    return sorted(set(bn)), sorted(set(up))
+
+
+def test_the_gpu_shapes_reach_every_regime_of_the_plans():
+    """``_neck_bwd.BN_REGIMES`` / ``UP_REGIMES`` against every shape the GPU op tests run; every new shape is there for a
+    regime nothing else reaches; and what a production call reaches, a GPU shape reaches.  2048 * 256, the quad count from
+    which ``ew_grid`` caps the element-wise grids, is not observable through the ABI: ``_neck_bwd.EW_CAP`` mirrors it by
+    reading."""
+    assert NB.missing_bn_regimes(NB.gpu_bn_shapes()) == []
+    assert NB.missing_up_regimes(NB.gpu_up_shapes()) == []
+    assert set(NB.missing_bn_regimes(NB.BN_SHAPES)) >= {
+        'slabs from the grid target', 'slabs == 1', 'slabs == 512', 'chunks == 2', 'element-wise grid capped',
+        'element-wise grid capped, total not a multiple of 2048 * 256'}                # what the toy shapes left out
+    assert set(NB.missing_up_regimes([s + (f,) for s in NB.UP_SHAPES for f in (2, 4, 8)])) >= {
+        'slabs from the grid target', 'up_gx grid capped'}
+    for i, s in enumerate(NB.BN_PLAN_SHAPES):
+        assert NB.missing_bn_regimes(NB.BN_SHAPES + NB.BN_PLAN_SHAPES[:i] + NB.BN_PLAN_SHAPES[i + 1:]) != [], s
+    small = [s + (f,) for s in NB.UP_SHAPES for f in (2, 4, 8)]
+    for i, s in enumerate(NB.UP_PLAN_SHAPES):
+        rest = NB.UP_PLAN_SHAPES[:i] + NB.UP_PLAN_SHAPES[i + 1:]
+        assert NB.missing_up_regimes(small + [t + (f,) for t, f in rest]) != [], s
+    bn, up = _production_calls()
+    assert set(NB.reached_bn_regimes(bn)) <= set(NB.reached_bn_regimes(NB.gpu_bn_shapes()))
+    assert set(NB.reached_up_regimes(up)) <= set(NB.reached_up_regimes(NB.gpu_up_shapes()))
+    assert {'slabs == 512', 'element-wise grid capped'} <= set(NB.reached_bn_regimes(bn))        # production is past the toy sizes
+    # the figures the comments of the shape lists give
+    a, b, c, d = (NB.bn_plan(*s) for s in NB.BN_PLAN_SHAPES)
+    assert (a['slabs'], a['pixPerSlab'], a['last_slab_pixels'], a['quads'], a['ew_grid']) == (512, 384, 372, 786384, 2048)
+    assert (b['chunks'], b['wanted'], b['slabs'], b['quads']) == (2, 256, 231, 591360)
+    assert (c['cw'], c['dead_threads'], c['slabs'], c['quads']) == (33, 25, 484, 558360)
+    assert (d['slabs'], d['last_slab_pixels'], d['pixPerSlab']) == (1, 240, 256)
+    u = [NB.up_plan(*s, f) for s, f in NB.UP_PLAN_SHAPES]
+    assert [(v['chunks'], v['wanted'], v['slabs']) for v in u] == [(1, 512, 480), (3, 171, 160), (1, 512, 512)]
+    assert [v['ew_capped'] for v in u] == [False, False, True] and u[2]['quads'] == 540672
+    assert NB.ew_plan(NB.EW_CAP - 1) == dict(quads=NB.EW_CAP - 1, ew_capped=False, ew_grid=2048, ew_ragged=False)
+    assert NB.ew_plan(NB.EW_CAP)['ew_capped'] and not NB.ew_plan(NB.EW_CAP)['ew_ragged']
+
+
+def test_the_restated_plans_give_the_librarys_workspace_sizes_at_the_plan_shapes(lib):
+    keep, p = _ptr()
+    for N, H, W, C in NB.BN_PLAN_SHAPES:
+        for ld in (None, C + 8):
+            d = _bn_desc(p, N, H, W, C, ld=ld)
+            assert lib.ct_bn_workspace_bytes(ctypes.byref(d)) == NB.bn_plan(N, H, W, C)['bytes'] > 0, (N, H, W, C)
+    for (N, H, W, C), f in NB.UP_PLAN_SHAPES:
+        d = _up_desc(p, N, H, W, C, f)
+        assert lib.ct_upsample_add_backward_workspace_bytes(ctypes.byref(d)) == NB.up_plan(N, H, W, C, f)['bytes'] > 0, (N, H, W, C, f)
+
+
+@pytest.mark.parametrize('batch', [True, False], ids=['batch-stats', 'running-stats'])
+@pytest.mark.parametrize('shape', NB.BN_PLAN_SHAPES, ids=str)
+def test_the_float32_reference_stays_inside_the_mask_cap_at_the_plan_shapes(shape, batch):
+    """what tests/test_hip_neck_backward.py holds the HIP forward's ReLU mask to (``check_mask``: flips only within 64 e32 of
+    0, on at most 0.1 % of the map), held by the float32 CPU run of the same case"""
+    case = NB.bn_case(shape)
+    (pre64, y64), (pre32, y32) = (NB.bn_free_run(case, dt, batch) for dt in (torch.float64, torch.float32))
+    flipped, near = NB.check_mask(pre32 > 0, pre64, NB.err(y32, y64), str(shape))
+    print('%s: fp32 torch flips %d units, %d of %d within the threshold' % (shape, flipped, near, pre64.numel()))
+
+
 def test_module_names_shapes_and_initialisation():
     from centertrack_amd import dla_up, model, weights
     from centertrack_amd._lib import CTError
