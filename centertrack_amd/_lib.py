@@ -167,6 +167,23 @@ class BnActDesc(ctypes.Structure):
                                   ('gres', ctypes.c_void_p), ('ldgres', ctypes.c_int)]
 
 
+class StemConvDesc(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('inp', ctypes.c_void_p * 3), ('w', ctypes.c_void_p * 3),
+                ('z', ctypes.c_void_p * 3), ('ldz', ctypes.c_int * 3),
+                ('gz', ctypes.c_void_p * 3), ('ldgz', ctypes.c_int * 3),
+                ('gw', ctypes.c_void_p * 3), ('gin', ctypes.c_void_p * 3),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
+class StemSumDesc(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('z', ctypes.c_void_p * 3), ('ldz', ctypes.c_int * 3),
+                ('mean', ctypes.c_void_p * 3), ('invstd', ctypes.c_void_p * 3),
+                ('gamma', ctypes.c_void_p * 3), ('beta', ctypes.c_void_p * 3),
+                ('y', ctypes.c_void_p), ('ldy', ctypes.c_int)]
+
+
 CT_MAX_FUSED_HEADS = 8
 
 
@@ -279,6 +296,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_upsample_add_backward', 'ct_upsample_add_backward_workspace_bytes', 'ct_dcn_mask_sigmoid_backward',
            'ct_conv2d_s2_backward', 'ct_conv2d_s2_backward_workspace_bytes', 'ct_packed_conv_weight_s2t_elems', 'ct_pack_conv_weight_s2t',
            'ct_bn_act_apply', 'ct_bn_act_backward', 'ct_bn_act_workspace_bytes', 'ct_maxpool2x2_backward', 'ct_stem_forward',
+           'ct_stem_conv_forward', 'ct_stem_conv_backward', 'ct_stem_conv_backward_workspace_bytes', 'ct_stem_bn_relu_sum',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
            'ct_decode_pose', 'ct_render_pre_hm',
@@ -374,6 +392,11 @@ def load():
     lib.ct_bn_act_workspace_bytes.restype = sz
     lib.ct_bn_act_workspace_bytes.argtypes = [ctypes.POINTER(BnActDesc)]
     lib.ct_maxpool2x2_backward.argtypes = [p, i, i, i, i, i, p, i, p, i, p, i, p]
+    lib.ct_stem_conv_forward.argtypes = [ctypes.POINTER(StemConvDesc), p]
+    lib.ct_stem_conv_backward.argtypes = [ctypes.POINTER(StemConvDesc), p]
+    lib.ct_stem_conv_backward_workspace_bytes.restype = sz
+    lib.ct_stem_conv_backward_workspace_bytes.argtypes = [ctypes.POINTER(StemConvDesc)]
+    lib.ct_stem_bn_relu_sum.argtypes = [ctypes.POINTER(StemSumDesc), p]
     lib.ct_stem_forward.argtypes = [p, p, p, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_stem_forward_parts.argtypes = [p, p, p, p, i, i, i, i, p, p, p, p, p, p, i, p]
     lib.ct_maxpool2x2.argtypes = [p, i, i, i, i, i, p, i, p]

@@ -18,8 +18,14 @@ when, and only when, the BatchNorm is in training mode, and then the running sta
 recorded only under ``dcn_v2.trainable()`` with autograd enabled; otherwise the same forward runs with nothing saved and
 returns the same bits.  CUDA fp32 tensors only: there is no CPU fallback.
 
-Not covered: the three 7x7 stems (``base_layer``, ``pre_img_layer``, ``pre_hm_layer``) are ``nn.Sequential`` modules that
-torch runs (NCHW; their sum is converted once); ``Bottleneck`` / ``BottleneckX``; dilation; nothing is ever downloaded."""
+The three 7x7 stems (``base_layer``, ``pre_img_layer``, ``pre_hm_layer``) stay ``nn.Sequential(Conv2d, BatchNorm2d, ReLU)``
+parameter holders and run as one autograd node on the kernels of DESIGN.md section 14: ``ct_stem_conv_forward`` (the raw
+``z`` of every stem present, NCHW planes in, NHWC out), ``ct_bn_stats`` per stem (training mode only) and
+``ct_stem_bn_relu_sum`` (BatchNorm, ReLU and the sum in one pass); the backward is ``ct_bn_relu_backward`` per stem on the
+incoming gradient itself, then ``ct_stem_conv_backward``.  The images never leave NCHW and nothing behind them is NCHW.
+
+Not covered: a first width other than 16 (such a ``DLA`` keeps the torch stems; NCHW, their sum is converted once);
+``Bottleneck`` / ``BottleneckX``; dilation; nothing is ever downloaded."""
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
@@ -28,8 +34,8 @@ from . import _lib, ops
 from .dla_up import BN_MOMENTUM, _recording, _ToNCHW, _ToNHWC, update_running_stats
 from .ops import View
 
-# None = off; a list receives, in call order, the NHWC output of every conv-BN-act unit, of every pool and (as NHWC views of
-# the NCHW maps) of every stem: what a float64 truth needs to take the ReLU masks and pool selections of this forward
+# None = off; a list receives, in call order, the NHWC output of every conv-BN-act unit, of every pool and of every stem
+# (ahead of their sum): what a float64 truth needs to take the ReLU masks and pool selections of this forward
 trace = None
 
 
@@ -189,6 +195,85 @@ def _maxpool(x):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the 7x7 stems: sum_s relu(bn_s(conv7x7_s(in_s)))
+
+def _stems_forward(inputs, layers):
+    """``inputs`` = (x, pre_img, pre_hm) as contiguous NCHW tensors (None = absent), ``layers`` = their ``nn.Sequential`` ->
+    (the NHWC view of the sum, what a backward needs).  With the trace on, every term is emitted ahead of the sum."""
+    live = [s for s in range(3) if inputs[s] is not None]
+    zs = ops.stem_conv_forward(inputs, [None if layers[s] is None else layers[s][0].weight.detach() for s in range(3)])
+    means, invstds, batches = [None] * 3, [None] * 3, [False] * 3
+    for s in live:
+        bn, z = layers[s][1], zs[s]
+        batch = bn.training or bn.running_mean is None
+        if batch:
+            P = z.N * z.H * z.W
+            if P == 1:
+                raise _lib.CTError('backbone: training-mode BatchNorm needs more than one value per channel (N*H*W == 1)')
+            mean, var, invstd = ops.bn_stats(z, bn.eps)
+            if bn.training and bn.running_mean is not None:
+                update_running_stats(bn, mean, var, P)
+        else:
+            mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+        means[s], invstds[s], batches[s] = mean, invstd, batch
+    gammas = [layers[s][1].weight.detach() if s in live else None for s in range(3)]
+    betas = [layers[s][1].bias.detach() if s in live else None for s in range(3)]
+    if trace is not None:
+        for s in live:
+            _emit(ops.bn_relu_apply(zs[s], means[s], invstds[s], gammas[s], betas[s]).buf)
+    y = ops.stem_bn_relu_sum(zs, means, invstds, gammas, betas)
+    return y, (zs, means, invstds, batches)
+
+
+class _StemsFunction(torch.autograd.Function):
+    """The three stems and their sum as one node: NCHW images -> the NHWC ``[N,H,W,16]`` sum.  Saved: the inputs, every raw
+    convolution output ``z_s`` and the statistics (private to the call, kept on ctx as ``_ConvBnActFunction`` does); the ReLU
+    masks are recomputed from them with the forward's own arithmetic.  Since the output is a plain sum, every stem's output
+    gradient is the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, pre_img, pre_hm, w0, w1, w2, g0, g1, g2, b0, b1, b2, layers):
+        inputs = (x, pre_img, pre_hm)
+        y, (zs, means, invstds, batches) = _stems_forward(inputs, layers)
+        ctx.zs, ctx.invstds, ctx.batches = zs, invstds, batches
+        ctx.means = [m if m is None or b else m.clone() for m, b in zip(means, batches)]
+        ctx.save_for_backward(x, pre_img, pre_hm, w0, w1, w2, g0, g1, g2, b0, b1, b2)
+        return y.buf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        saved = ctx.saved_tensors
+        inputs, ws, gammas, betas = saved[0:3], saved[3:6], saved[6:9], saved[9:12]
+        need = ctx.needs_input_grad
+        gyv = View(gy.contiguous())
+        gzs, gg, gb = [None] * 3, [None] * 3, [None] * 3
+        need_in = [inputs[s] is not None and need[s] for s in range(3)]
+        need_w = [inputs[s] is not None and need[3 + s] for s in range(3)]
+        for s in range(3):
+            if inputs[s] is None:
+                continue
+            gzs[s], gg[s], gb[s] = ops.bn_relu_backward(ctx.zs[s], gyv, ctx.means[s], ctx.invstds[s], gammas[s].detach(),
+                                                        betas[s].detach(), ctx.batches[s], need_z=need_in[s] or need_w[s],
+                                                        need_gamma=need[6 + s], need_beta=need[9 + s])
+        gw, gin = ops.stem_conv_backward(gzs, inputs, [None if w is None else w.detach() for w in ws], need_w=need_w,
+                                         need_in=need_in)
+        return tuple(gin) + tuple(gw) + tuple(gg) + tuple(gb) + (None,)
+
+
+def _stems(inputs, layers):
+    """The stems on NCHW tensors -> the NHWC ``[N,H,W,16]`` tensor of their sum"""
+    inputs = tuple(None if t is None else t.contiguous() for t in inputs)
+    if _recording():
+        # the parameters are read from the modules at every call: three weights, three gammas, three betas
+        par = [None if m is None else p(m) for p in (lambda m: m[0].weight, lambda m: m[1].weight, lambda m: m[1].bias)
+               for m in layers]
+        return _StemsFunction.apply(*(inputs + tuple(par) + (layers,)))
+    with torch.no_grad():
+        return _stems_forward(inputs, layers)[0].buf
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the modules
 
 def _no_dilation(dilation):
@@ -316,7 +401,7 @@ class Tree(nn.Module):
 class DLA(nn.Module):
     """Reference ``DLA(levels, channels, num_classes=1000, block=BasicBlock, residual_root=False, linear_root=False,
     opt=None)``.  ``forward(x, pre_img=None, pre_hm=None)`` returns the six level outputs (NCHW), ``forward_nhwc`` the same as
-    ``[N,H,W,C]`` tensors.  The stems are torch modules."""
+    ``[N,H,W,C]`` tensors.  With ``channels[0] == 16`` the stems run on this package's kernels (``_StemsFunction``), else on torch."""
 
     def __init__(self, levels, channels, num_classes=1000, block=BasicBlock, residual_root=False, linear_root=False, opt=None):
         super().__init__()
@@ -352,26 +437,42 @@ class DLA(nn.Module):
             inplanes = planes
         return nn.Sequential(*modules)
 
-    def _stems(self, x, pre_img, pre_hm):
+    def _stem_parts(self, x, pre_img, pre_hm):
+        """[(stem, its input)] for x, pre_img, pre_hm; (None, None) where the input is absent"""
         parts = [(self.base_layer, x)]
         for name, t in (('pre_img_layer', pre_img), ('pre_hm_layer', pre_hm)):
+            if t is not None and not hasattr(self, name):
+                raise _lib.CTError('DLA: built without %s (opt.%s)' % (name, name[:-len('_layer')]))
+            parts.append((getattr(self, name), t) if t is not None else (None, None))
+        for _, t in parts:
             if t is not None:
-                if not hasattr(self, name):
-                    raise _lib.CTError('DLA: built without %s (opt.%s)' % (name, name[:-len('_layer')]))
-                parts.append((getattr(self, name), t))
+                _need_cuda(t)
+        return parts
+
+    def _stems(self, x, pre_img, pre_hm):
+        """the torch stems of a first width other than 16 -> the NCHW sum"""
         y = None
-        for layer, t in parts:
-            _need_cuda(t)
+        for layer, t in self._stem_parts(x, pre_img, pre_hm):
+            if t is None:
+                continue
             s = layer(t)
             _emit(s.permute(0, 2, 3, 1))
             y = s if y is None else y + s
         return y
 
     def forward_nhwc(self, x, pre_img=None, pre_hm=None):
-        """NCHW inputs (the stems are torch's) -> the six level outputs as ``[N,H,W,C]`` tensors"""
-        with torch.set_grad_enabled(_recording()):
-            y = self._stems(x, pre_img, pre_hm)
-        y = to_nhwc(y)
+        """NCHW images -> the six level outputs as ``[N,H,W,C]`` tensors"""
+        if self.channels[0] == 16:
+            parts = self._stem_parts(x, pre_img, pre_hm)
+            y = _stems([t for _, t in parts], [m for m, _ in parts])
+        else:
+            with torch.set_grad_enabled(_recording()):
+                y = self._stems(x, pre_img, pre_hm)
+            y = to_nhwc(y)
+        return self._levels_nhwc(y)
+
+    def _levels_nhwc(self, y):
+        """the six levels on the NHWC sum of the stems"""
         out = []
         for i in range(6):
             level = getattr(self, 'level{}'.format(i))

@@ -297,6 +297,16 @@ class DLAUp(nn.Module):
             scales[j + 1:] = scales[j]
             in_channels[j + 1:] = [channels[j] for _ in channels[j + 1:]]
 
+    def forward_nhwc(self, layers):
+        """``forward`` on a list of ``[N,H,W,C]`` tensors, with its in-place semantics (``layers[startp + 1:]`` are rewritten)
+        and no conversion: every returned tensor is an entry of ``layers``"""
+        n = len(layers)
+        out = [layers[-1]]
+        for i in range(n - self.startp - 1):
+            getattr(self, 'ida_{}'.format(i)).forward_nhwc(layers, n - i - 2, n)
+            out.insert(0, layers[-1])
+        return out
+
     def forward(self, layers):
         n = len(layers)
         out = [layers[-1]]

@@ -60,20 +60,48 @@ class _HeadsFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, *gouts):
-        names, nh = ctx.names, len(ctx.names)
-        p = [t.detach() for t in ctx.saved_tensors]
-        need = ctx.needs_input_grad
-        hc = p[0].shape[0]
-        needs = {'x': need[1], 'w0': any(need[2 + 4 * j] for j in range(nh)), 'b0': any(need[3 + 4 * j] for j in range(nh)),
-                 'w2': {h: need[4 + 4 * j] for j, h in enumerate(names)}, 'b2': {h: need[5 + 4 * j] for j, h in enumerate(names)}}
-        w0 = torch.cat(p[0::4], 0) if needs['x'] else None
-        res = ops.heads_backward(ctx.x, ctx.mid, dict(zip(names, gouts)), w0, OrderedDict(zip(names, p[2::4])), needs)
-        grads = [None, ops.view_to_nchw(res['x']) if needs['x'] else None]
-        for j, h in enumerate(names):
-            grads += [res['w0'][hc * j:hc * (j + 1)] if need[2 + 4 * j] else None,
-                      res['b0'][hc * j:hc * (j + 1)] if need[3 + 4 * j] else None,
-                      res['w2'][h] if need[4 + 4 * j] else None, res['b2'][h] if need[5 + 4 * j] else None]
-        return tuple(grads)
+        res, grads = _heads_gradients(ctx.names, ctx.x, ctx.mid, ctx.saved_tensors, ctx.needs_input_grad, gouts)
+        return (None, ops.view_to_nchw(res['x']) if ctx.needs_input_grad[1] else None) + grads
+
+
+def _heads_gradients(names, x, mid, params, need, gouts):
+    """what both heads functions compute in backward -> (``ops.heads_backward``'s result, the parameter gradients in the order
+    of ``params``); ``need`` = the function's ``needs_input_grad`` (names, feat, *params)"""
+    nh = len(names)
+    p = [t.detach() for t in params]
+    hc = p[0].shape[0]
+    needs = {'x': need[1], 'w0': any(need[2 + 4 * j] for j in range(nh)), 'b0': any(need[3 + 4 * j] for j in range(nh)),
+             'w2': {h: need[4 + 4 * j] for j, h in enumerate(names)}, 'b2': {h: need[5 + 4 * j] for j, h in enumerate(names)}}
+    w0 = torch.cat(p[0::4], 0) if needs['x'] else None
+    res = ops.heads_backward(x, mid, dict(zip(names, gouts)), w0, OrderedDict(zip(names, p[2::4])), needs)
+    grads = []
+    for j, h in enumerate(names):
+        grads += [res['w0'][hc * j:hc * (j + 1)] if need[2 + 4 * j] else None,
+                  res['b0'][hc * j:hc * (j + 1)] if need[3 + 4 * j] else None,
+                  res['w2'][h] if need[4 + 4 * j] else None, res['b2'][h] if need[5 + 4 * j] else None]
+    return res, tuple(grads)
+
+
+class _HeadsNHWCFunction(torch.autograd.Function):
+    """``_HeadsFunction`` over a contiguous ``[N,H,W,C]`` tensor that takes part in autograd: nothing is converted on the way
+    in, and the input gradient leaves as the NHWC tensor ``ops.heads_backward`` produces."""
+
+    @staticmethod
+    def forward(ctx, names, feat, *params):
+        p = [t.detach() for t in params]
+        outs, mid = ops.heads_forward_train(ops.View(feat.detach()), torch.cat(p[0::4], 0), torch.cat(p[1::4], 0),
+                                            OrderedDict(zip(names, p[2::4])), OrderedDict(zip(names, p[3::4])))
+        if any(ctx.needs_input_grad):
+            ctx.names, ctx.mid = names, mid
+            ctx.save_for_backward(feat, *params)
+        return tuple(outs.values())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gouts):
+        feat, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        res, grads = _heads_gradients(ctx.names, ops.View(feat.detach()), ctx.mid, params, ctx.needs_input_grad, gouts)
+        return (None, res['x'].buf if ctx.needs_input_grad[1] else None) + grads
 
 
 class FusedHeads(nn.Module):
@@ -129,6 +157,23 @@ class FusedHeads(nn.Module):
             raise _lib.CTError('FusedHeads was built for %d input channels (got %d)' % (self.in_channels, cin))
         params = [t for h in self.heads for t in self.head_parameters(h)]
         outs = _HeadsFunction.apply(tuple(self.heads), feat, *params)
+        return OrderedDict(zip(self.heads, outs))
+
+
+    def forward_nhwc(self, feat):
+        """``feat``: an ``[N,H,W,in_channels]`` fp32 CUDA tensor (the layout of every trainable module's ``forward_nhwc``),
+        part of the autograd graph -> the same ``OrderedDict`` of NCHW logits, the same bits as ``forward`` on the NCHW
+        form of ``feat``; the input gradient is NHWC."""
+        if not torch.is_tensor(feat) or feat.dim() != 4:
+            raise _lib.CTError('FusedHeads.forward_nhwc takes an [N,H,W,C] tensor')
+        if feat.dtype != torch.float32:
+            raise _lib.CTError('FusedHeads computes in fp32 (got %s)' % feat.dtype)
+        if feat.device.type != 'cuda':
+            raise _lib.CTError('FusedHeads runs on an MI355X only (got a %s tensor); no CPU fallback' % feat.device)
+        if feat.shape[3] != self.in_channels:
+            raise _lib.CTError('FusedHeads was built for %d input channels (got %d)' % (self.in_channels, feat.shape[3]))
+        params = [t for h in self.heads for t in self.head_parameters(h)]
+        outs = _HeadsNHWCFunction.apply(tuple(self.heads), feat.contiguous(), *params)
         return OrderedDict(zip(self.heads, outs))
 
 

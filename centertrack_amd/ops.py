@@ -744,6 +744,122 @@ def maxpool2x2_backward(x, gy, add=None, out=None):
     return out
 
 
+STEM_CIN = (3, 3, 1)
+
+
+def _stem_planes(t, s, N, H, W, dev, what):
+    """a contiguous fp32 NCHW input (or image gradient) of stem ``s``"""
+    if (t.dim() != 4 or tuple(t.shape) != (N, STEM_CIN[s], H, W) or t.dtype != torch.float32 or not t.is_contiguous()
+            or t.device != dev):
+        raise _lib.CTError('%s: stem %d wants a contiguous fp32 [%d,%d,%d,%d] tensor on %s (got %s)' % (
+            what, s, N, STEM_CIN[s], H, W, dev, tuple(t.shape)))
+    return t
+
+
+def _stem_weight(t, s, dev, what):
+    if tuple(t.shape) != (16, STEM_CIN[s], 7, 7) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+        raise _lib.CTError('%s: stem %d wants a contiguous fp32 [16,%d,7,7] weight on %s (got %s)' % (
+            what, s, STEM_CIN[s], dev, tuple(t.shape)))
+    return t
+
+
+def stem_conv_forward(inputs, weights, out=None):
+    """``z_s = conv7x7(inputs[s], weights[s])`` (pad 3, no bias) for every stem present: ``inputs`` = (x, pre_img, pre_hm) as
+    contiguous NCHW tensors, ``None`` = stem absent (x must be given); ``weights``: the OIHW [16,Cin,7,7] weights; ``out``:
+    optional caller-owned 16-channel views.  -> a list of three NHWC views (None for an absent stem).  One launch."""
+    lib = _lib.load()
+    if inputs[0] is None:
+        raise _lib.CTError('stem_conv_forward: the image stem is part of every call')
+    N, _, H, W = inputs[0].shape
+    dev = inputs[0].device
+    d = _lib.StemConvDesc()
+    d.N, d.H, d.W = N, H, W
+    zs = [None, None, None]
+    for s in range(3):
+        if inputs[s] is None:
+            continue
+        d.inp[s] = _stem_planes(inputs[s], s, N, H, W, dev, 'stem_conv_forward').data_ptr()
+        d.w[s] = _stem_weight(weights[s], s, dev, 'stem_conv_forward').data_ptr()
+        zs[s] = out[s] if out is not None and out[s] is not None else new_view(N, H, W, 16, dev)
+        if (zs[s].N, zs[s].H, zs[s].W, zs[s].C) != (N, H, W, 16):
+            raise _lib.CTError('stem_conv_forward: out[%d] is not a [%d,%d,%d,16] view' % (s, N, H, W))
+        d.z[s], d.ldz[s] = zs[s].ptr, zs[s].ld
+    _lib.check(lib.ct_stem_conv_forward(ctypes.byref(d), _lib.stream_ptr()), 'ct_stem_conv_forward')
+    return zs
+
+
+def stem_bn_relu_sum(zs, means, invstds, gammas, betas, out=None):
+    """``y = sum_s max(0, fma(z_s - mean_s, gamma_s * invstd_s, beta_s))`` over the stems present (``zs[s]`` a 16-channel NHWC
+    view or None; ``zs[0]`` must be given), added in the order x, pre_img, pre_hm; each term has the bits of
+    ``bn_relu_apply``.  One pass; allocates ``out`` if not given."""
+    lib = _lib.load()
+    if zs[0] is None:
+        raise _lib.CTError('stem_bn_relu_sum: the image stem is part of every call')
+    z0 = zs[0]
+    if out is None:
+        out = new_view(z0.N, z0.H, z0.W, 16, z0.buf.device)
+    d = _lib.StemSumDesc()
+    d.N, d.H, d.W = z0.N, z0.H, z0.W
+    for s in range(3):
+        z = zs[s]
+        if z is None:
+            continue
+        if (z.N, z.H, z.W, z.C) != (z0.N, z0.H, z0.W, 16):
+            raise _lib.CTError('stem_bn_relu_sum: z[%d] does not have the shape of z[0] with 16 channels' % s)
+        d.z[s], d.ldz[s] = z.ptr, z.ld
+        d.mean[s], d.invstd[s], d.gamma[s], d.beta[s] = (_bn_vec(t[s], 16, z).data_ptr() for t in (means, invstds, gammas, betas))
+    if (out.N, out.H, out.W, out.C) != (z0.N, z0.H, z0.W, 16):
+        raise _lib.CTError('stem_bn_relu_sum: out does not have the shape of z[0]')
+    d.y, d.ldy = out.ptr, out.ld
+    _lib.check(lib.ct_stem_bn_relu_sum(ctypes.byref(d), _lib.stream_ptr()), 'ct_stem_bn_relu_sum')
+    return out
+
+
+def stem_conv_backward(gzs, inputs=(None, None, None), weights=(None, None, None), need_w=(True, True, True),
+                       need_in=(False, False, False), gws=None, gins=None):
+    """Gradients of ``stem_conv_forward`` for the gradients ``gzs[s]`` of ``z_s`` (16-channel NHWC views, None = stem absent)
+    -> ``(gw list, gin list)``: ``gw[s]`` OIHW (needs ``inputs[s]``) where ``need_w[s]``, ``gin[s]`` NCHW (needs
+    ``weights[s]``) where ``need_in[s]``, None for what was not asked for: no buffer is allocated and no kernel runs for
+    those.  ``gws`` / ``gins``: optional caller-owned outputs.  Bitwise reproducible."""
+    lib = _lib.load()
+    what = 'stem_conv_backward'
+    live = [s for s in range(3) if gzs[s] is not None and (need_w[s] or need_in[s])]
+    gw, gin = [None, None, None], [None, None, None]
+    if not live:
+        return gw, gin
+    g0 = gzs[live[0]]
+    N, H, W, dev = g0.N, g0.H, g0.W, g0.buf.device
+    d = _lib.StemConvDesc()
+    d.N, d.H, d.W = N, H, W
+    for s in live:
+        g = gzs[s]
+        if (g.N, g.H, g.W, g.C) != (N, H, W, 16):
+            raise _lib.CTError('%s: gz[%d] is not a [%d,%d,%d,16] view' % (what, s, N, H, W))
+        d.gz[s], d.ldgz[s] = g.ptr, g.ld
+        if need_w[s]:
+            if inputs[s] is None:
+                raise _lib.CTError('%s: the weight gradient of stem %d needs its input' % (what, s))
+            d.inp[s] = _stem_planes(inputs[s], s, N, H, W, dev, what).data_ptr()
+            gw[s] = (_stem_weight(gws[s], s, dev, what) if gws is not None and gws[s] is not None
+                     else torch.empty((16, STEM_CIN[s], 7, 7), dtype=torch.float32, device=dev))
+            d.gw[s] = gw[s].data_ptr()
+        if need_in[s]:
+            if weights[s] is None:
+                raise _lib.CTError('%s: the image gradient of stem %d needs its weight' % (what, s))
+            d.w[s] = _stem_weight(weights[s], s, dev, what).data_ptr()
+            gin[s] = (_stem_planes(gins[s], s, N, H, W, dev, what) if gins is not None and gins[s] is not None
+                      else torch.empty((N, STEM_CIN[s], H, W), dtype=torch.float32, device=dev))
+            d.gin[s] = gin[s].data_ptr()
+    if any(g is not None for g in gw):
+        need = lib.ct_stem_conv_backward_workspace_bytes(ctypes.byref(d))
+        if not need:
+            raise _lib.CTError('ct_stem_conv_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
+        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    _lib.check(lib.ct_stem_conv_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_stem_conv_backward')
+    return gw, gin
+
+
 # field order of a packed decode row after (score, cls, xs0, ys0)
 _DECODE_REST = ['tracking', 'dep', 'rot', 'dim', 'amodel_offset', 'nuscenes_att', 'velocity']
 

@@ -474,6 +474,46 @@ size_t ct_bn_act_workspace_bytes(const ct_bn_act_desc *d);
 int ct_maxpool2x2_backward(const float *x, int N, int H, int W, int C, int ldx, const float *gy, int ldgy,
                            const float *add, int ldadd, float *gx, int ldgx, void *stream);
 
+/* ---- the trainable 7x7 stems (base_layer / pre_img_layer / pre_hm_layer, dla.py:238-267,305-311); additions under ABI 103.
+ * Specialised to Cout = 16 and Cin = 3, 3, 1 (index s = 0 image, 1 previous image, 2 prior heat-map).  Inputs and image
+ * gradients are the reference's contiguous NCHW planes, weights and weight gradients OIHW [16,Cin,7,7]; every 16-channel map is
+ * an NHWC view with a pitch under the rules of the neck block above (ld >= 16, ld % 4 == 0, 16-byte aligned pointers, a view
+ * below 2 GiB).  All fp32, no atomics, every sum in a fixed order, slab counts from the shapes only: bitwise equal from run to
+ * run.  The forward of a training step is ct_stem_conv_forward, ct_bn_stats per stem, ct_stem_bn_relu_sum; since y is a plain
+ * sum, each stem's output gradient is gy itself: the backward is ct_bn_relu_backward(z_s, gy) per stem, then
+ * ct_stem_conv_backward.
+ *
+ * ct_stem_conv_forward: for every s with in[s] != NULL (in[0] must be given): z[s] = conv7x7(in[s], w[s]), pad 3, no bias -- the
+ *   raw convolution output that training-mode BatchNorm needs -- on the fp32 MFMA, one launch for all stems present.
+ * ct_stem_conv_backward: for every s, from gz[s] (the gradient of z[s]):
+ *   gw[s][co,ci,ky,kx] = sum_{n,y,x} gz[s][n,y,x,co] * in[s][n,ci,y+ky-3,x+kx-3] (zero outside the image) when gw[s] != NULL: on
+ *     the fp32 MFMA, partial sums in slabs of `workspace` (ct_stem_conv_backward_workspace_bytes(d) bytes, 0 for a rejected
+ *     descriptor or when no gw is asked for), a second launch adds the slabs in slab order; one pair of launches for all stems;
+ *   gin[s][n,ci,y,x] = sum_{ky,kx,co} gz[s][n,y-ky+3,x-kx+3,co] * w[s][co,ci,ky,kx] when gin[s] != NULL (needs w[s], not in[s]).
+ *   Nothing is read, written or launched for an output that is NULL; at least one must be asked for.
+ * ct_stem_bn_relu_sum: y = sum_s max(0, fma(z[s] - mean[s], a, beta[s])), a = gamma[s] * invstd[s], over the stems with
+ *   z[s] != NULL (z[0] must be given), added in the order 0, 1, 2; each term has the bits of ct_bn_relu_apply. */
+typedef struct ct_stem_conv_desc {
+    int N, H, W;
+    const float *in[3];                         /* [N,Cin,H,W]; forward, gw */
+    const float *w[3];                          /* [16,Cin,7,7]; forward, gin */
+    float *z[3]; int ldz[3];                    /* forward: the outputs [N,H,W,16] */
+    const float *gz[3]; int ldgz[3];            /* backward: the gradients of z */
+    float *gw[3];                               /* backward: [16,Cin,7,7] or NULL */
+    float *gin[3];                              /* backward: [N,Cin,H,W] or NULL */
+    float *workspace; size_t workspace_bytes;   /* backward with a gw */
+} ct_stem_conv_desc;
+int ct_stem_conv_forward(const ct_stem_conv_desc *d, void *stream);
+int ct_stem_conv_backward(const ct_stem_conv_desc *d, void *stream);
+size_t ct_stem_conv_backward_workspace_bytes(const ct_stem_conv_desc *d);
+typedef struct ct_stem_sum_desc {
+    int N, H, W;
+    const float *z[3]; int ldz[3];
+    const float *mean[3]; const float *invstd[3]; const float *gamma[3]; const float *beta[3];     /* [16] each, 16-byte aligned */
+    float *y; int ldy;
+} ct_stem_sum_desc;
+int ct_stem_bn_relu_sum(const ct_stem_sum_desc *d, void *stream);
+
 /* ---- the three 7x7 stems, fused --------------------------------------------------
  * Replaces DLA.forward's base_layer / pre_img_layer / pre_hm_layer and their sum
  * (dla.py:238-267,305-311): y = sum_s relu(bn_s(conv7x7_s(in_s))), inputs NCHW
