@@ -26,11 +26,9 @@
 //     modulated sample), are summed through LDS in wave order, and the workgroup stores its partial block into slab
 //     `blockIdx.y` of the workspace.  Units of tap 0 / channel block 0 also accumulate g_bias (B = 1).
 //   * dcn_bwd_reduce_kernel sums the slabs in slab order into g_weight (OIHW) and g_bias.  No float atomics on this side.
-#include "ct_common.h"
+#include "ct_train.h"
 
 namespace {
-
-constexpr int SENTINEL = (int)0x80000000;     // vector offset of a dropped / zero-reading buffer access (ct_common.h)
 
 struct BwdArgs {
     const float *x, *om, *gy, *wT;
@@ -44,16 +42,6 @@ struct BwdArgs {
     int stepsPerWave;   // weight kernel: 4-pixel steps per wave
     size_t slabStride;  // floats per slab: Cout*Cin*9 + Cout
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t view_rsrc(const float *p, size_t pixels, int ld, int C)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)(((pixels - 1) * ld + C) * 4u), 0x00020000);
-}
-
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, int voff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
-}
 
 // One bilinear sample of tap k at pixel (n, h, w): the linear cell index (over the batch) of corner 00 -- corner ab is cell
 // base + a * W + b --, one validity bit per corner (bit 2a + b; a cleared bit = contributes 0), the weights and the mask.  ys is formed as the oracle forms it (exact small integer + one fp32 add), so floor picks the same cell.
@@ -331,8 +319,6 @@ struct BwdPlan {
     int NT, tilesPerImg, CS, slabs, stepsPerWave, units;
     size_t slabStride;
 };
-
-const double VIEW_LIMIT = 2147483648.0;       // a buffer descriptor's byte offsets are 31-bit
 
 int make_plan(const ct_dcn_bwd_desc *d, BwdPlan *p, bool needBuffers)
 {

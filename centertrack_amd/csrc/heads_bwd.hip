@@ -3,8 +3,10 @@
 // section 11.  The input gradient of the first layer is a plain ct_conv2d of the hidden gradient with the transposed, flipped
 // weight and has no kernel here.
 //
-//   * conv_bwd_weight_kernel: gw[co, ci, tap] = sum_p gy[p, co] * x[p + tap, ci] (stride 1, pad ks / 2, zero outside the image),
-//     K = all pixels of the batch, on v_mfma_f32_16x16x4_f32.  The plan is dcn_bwd_weight_kernel's (dcn_bwd.hip): a workgroup
+//   * conv_bwd_weight_kernel<STRIDE>: gw[co, ci, tap] = sum_p gy[p, co] * x[STRIDE * p + tap, ci] (pad ks / 2, zero outside the
+//     image), K = all pixels of gy, on v_mfma_f32_16x16x4_f32.  <1> is ct_conv2d_backward_weight; <2> (3x3, no bias) is the weight
+//     half of ct_conv2d_s2_backward (backbone_bwd.hip), launched through ct_conv_s2_weight_launch (ct_train.h).
+//     The plan is dcn_bwd_weight_kernel's (dcn_bwd.hip): a workgroup
 //     owns one (tap, 32 input channels, up to 64 couts) block of the output and one K slab of pixels; its four waves split the
 //     slab, each stepping 4 pixels per MFMA (A = gy^T, B = the shifted x, both straight from global through buffer descriptors:
 //     a tap outside the image carries the sentinel offset and reads 0), are summed through LDS in wave order, and the workgroup
@@ -18,22 +20,9 @@
 //     pixels of the slab in ascending order; the partials go to slab `blockIdx.x` of the workspace and heads_tail_reduce_kernel
 //     adds them in slab order.
 // No atomics anywhere: every result is bitwise equal from run to run.
-#include "ct_common.h"
+#include "ct_train.h"
 
 namespace {
-
-constexpr int SENTINEL = (int)0x80000000;     // vector offset of a zero-reading buffer access (ct_common.h)
-const double VIEW_LIMIT = 2147483648.0;       // a buffer descriptor's byte offsets are 31-bit
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t view_rsrc(const float *p, size_t pixels, int ld, int C)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)(((pixels - 1) * ld + C) * 4u), 0x00020000);
-}
-
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, int voff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the weight gradient of a convolution
@@ -41,29 +30,33 @@ __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, int voff)
 struct CwArgs {
     const float *x, *gy;
     float *ws;
-    int N, H, W, Cin, Cout, ldx, ldgy;
-    int ks, NT, cgroups, withBias;
+    int N, H, W, Cin, Cout, ldx, ldgy;      // H, W: the grid of gy
+    int NT, cgroups;
     int stepsPerWave;   // 4-pixel steps per wave
-    size_t slabStride;  // floats per slab: Cout*Cin*ks*ks + Cout
+    size_t slabStride;  // floats per slab: Cout*Cin*ks*ks (+ Cout with a bias tail)
+    int Hi, Wi;         // stride 2: the grid of x (2H, 2W)
+    int ks, withBias;   // stride 1
 };
 
-constexpr int W_TILES = 12;      // accumulator tiles of a wave: 2 channel tiles x 4 cout tiles + 4 bias tiles
-
+// STRIDE 1: ks 1 or 3, pad ks / 2, any Cout, optional bias; 12 accumulator tiles of a wave: 2 channel tiles x 4 cout tiles + 4
+// bias tiles.  STRIDE 2: ks 3, pad 1, Cout % 16 == 0, no bias: 8 tiles.
+template <int STRIDE>
 __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(CwArgs a)
 {
+    constexpr int W_TILES = STRIDE == 1 ? 12 : 8;
     __shared__ float red[3][W_TILES][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int HW = a.H * a.W;
     const int total = a.N * HW;
-    const int taps = a.ks * a.ks;
+    const int taps = STRIDE == 1 ? a.ks * a.ks : 9;
     int unit = blockIdx.x;
     const int k = unit % taps;
     unit /= taps;
     const int cig = unit % a.cgroups, cog = unit / a.cgroups;
-    const int dy = a.ks == 3 ? k / 3 - 1 : 0, dx = a.ks == 3 ? k % 3 - 1 : 0;
-    const bool withBias = a.withBias && k == 0 && cig == 0;
+    const int dy = (STRIDE == 2 || a.ks == 3) ? k / 3 - 1 : 0, dx = (STRIDE == 2 || a.ks == 3) ? k % 3 - 1 : 0;
+    const bool withBias = STRIDE == 1 && a.withBias && k == 0 && cig == 0;
     const int nco = min(4, a.NT - cog * 4);
-    const __amdgpu_buffer_rsrc_t xrs = view_rsrc(a.x, (size_t)total, a.ldx, a.Cin);
+    const __amdgpu_buffer_rsrc_t xrs = view_rsrc(a.x, STRIDE == 1 ? (size_t)total : (size_t)a.N * a.Hi * a.Wi, a.ldx, a.Cin);
     const __amdgpu_buffer_rsrc_t gyrs = view_rsrc(a.gy, (size_t)total, a.ldgy, a.Cout);
     const int c0 = cig * 32 + (lane & 15);
     const bool has1 = c0 + 16 < a.Cin;                       // (Cin % 32 == 16: the last group is one tile wide)
@@ -73,7 +66,7 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(CwArgs a)
     const int nsteps = (total + 3) >> 2;
     const int s0 = min(nsteps, ((int)blockIdx.y * 4 + wave) * a.stepsPerWave);
     const int s1 = min(nsteps, s0 + a.stepsPerWave);
-    // four steps (16 pixels) per round: the loads of all four are in flight together
+    // four steps (16 pixels of gy) per round: the loads of all four are in flight together
     for (int st = s0; st < s1; st += 4) {
         float col[4][2], g[4][4];
 #pragma unroll
@@ -81,14 +74,22 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(CwArgs a)
             const int gp = (st + u) * 4 + (lane >> 4);
             const bool live = st + u < s1 && gp < total;
             const int n = gp / HW, pix = gp - n * HW, h = pix / a.W, w = pix - h * a.W;
-            const bool inside = live && h + dy >= 0 && h + dy < a.H && w + dx >= 0 && w + dx < a.W;
-            const int xo = (gp + dy * a.W + dx) * a.ldx;     // the shifted pixel of the same image
+            bool inside;
+            int xo;
+            if constexpr (STRIDE == 1) {
+                inside = live && h + dy >= 0 && h + dy < a.H && w + dx >= 0 && w + dx < a.W;
+                xo = (gp + dy * a.W + dx) * a.ldx;           // the shifted pixel of the same image
+            } else {
+                const int iy = 2 * h + dy, ix = 2 * w + dx;
+                inside = live && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi;
+                xo = ((n * a.Hi + iy) * a.Wi + ix) * a.ldx;
+            }
             col[u][0] = bload(xrs, inside ? (xo + c0) * 4 : SENTINEL);
             col[u][1] = bload(xrs, (inside && has1) ? (xo + c0 + 16) * 4 : SENTINEL);
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
                 const int co = (cog * 4 + ct) * 16 + (lane & 15);
-                g[u][ct] = bload(gyrs, (live && ct < nco && co < a.Cout) ? (gp * a.ldgy + co) * 4 : SENTINEL);
+                g[u][ct] = bload(gyrs, (live && ct < nco && (STRIDE == 2 || co < a.Cout)) ? (gp * a.ldgy + co) * 4 : SENTINEL);
             }
         }
 #pragma unroll
@@ -98,7 +99,9 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(CwArgs a)
                 if (ct < nco) {                                  // (uniform)
                     acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[u][ct], col[u][0], acc[ct], 0, 0, 0);
                     acc[4 + ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[u][ct], col[u][1], acc[4 + ct], 0, 0, 0);
-                    if (withBias) acc[8 + ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[u][ct], 1.0f, acc[8 + ct], 0, 0, 0);
+                    if constexpr (STRIDE == 1) {
+                        if (withBias) acc[8 + ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(g[u][ct], 1.0f, acc[8 + ct], 0, 0, 0);
+                    }
                 }
             }
         }
@@ -123,14 +126,17 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(CwArgs a)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int co = (cog * 4 + ct) * 16 + (lane >> 4) * 4 + e;
-            if (co >= a.Cout) continue;
+            if (STRIDE == 1 && co >= a.Cout) continue;
             slab[((size_t)co * a.Cin + c0) * taps + k] = acc[ct][e];
             if (has1) slab[((size_t)co * a.Cin + c0 + 16) * taps + k] = acc[4 + ct][e];
-            if (withBias && (lane & 15) == 0) slab[(size_t)a.Cout * a.Cin * taps + co] = acc[8 + ct][e];
+            if constexpr (STRIDE == 1) {
+                if (withBias && (lane & 15) == 0) slab[(size_t)a.Cout * a.Cin * taps + co] = acc[8 + ct][e];
+            }
         }
     }
 }
 
+// ws [slabs][slabStride] -> gw (the first nw floats of a slab) and gb (the rest, where asked for), slabs added in slab order
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float *ws, int slabs, size_t slabStride, size_t nw, float *gw,
                                                           float *gb)
 {
@@ -143,38 +149,34 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float *ws, int s
     else gb[i - nw] = s;
 }
 
-struct CwPlan {
-    int NT, cgroups, units, slabs, stepsPerWave;
-    size_t slabStride;
-};
+int launch_cw(const char *fn, int stride, CwArgs a, const CwPlan &p, float *gw, float *gb, hipStream_t s)
+{
+    a.NT = p.NT; a.cgroups = p.cgroups; a.stepsPerWave = p.stepsPerWave; a.slabStride = p.slabStride;
+    const dim3 grid((unsigned)p.units, (unsigned)p.slabs);
+    if (stride == 1) hipLaunchKernelGGL(conv_bwd_weight_kernel<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(conv_bwd_weight_kernel<2>, grid, dim3(256), 0, s, a);
+    CT_CHECK_LAUNCH(fn);
+    const size_t nw = (size_t)a.Cout * a.Cin * a.ks * a.ks;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((p.slabStride + 255) / 256)), dim3(256), 0, s, a.ws, p.slabs, p.slabStride,
+                       nw, gw, gb);
+    CT_CHECK_LAUNCH(fn);
+    return CT_OK;
+}
 
 int make_cw_plan(const ct_conv_bwd_weight_desc *d, CwPlan *p, bool needBuffers)
 {
-    if (!d) CT_FAIL_ARG("ct_conv2d_backward_weight: null descriptor");
-    if (d->ks != 1 && d->ks != 3) CT_FAIL_ARG("ct_conv2d_backward_weight: ks=%d unsupported (1 or 3)", d->ks);
-    if (d->stride != 1) CT_FAIL_ARG("ct_conv2d_backward_weight: stride=%d unsupported (1)", d->stride);
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) CT_FAIL_ARG("ct_conv2d_backward_weight: bad shape");
-    if (d->Cin % 16 || d->Cin <= 0) CT_FAIL_ARG("ct_conv2d_backward_weight: Cin=%d must be a positive multiple of 16", d->Cin);
-    if (needBuffers && (!d->x || !d->gy || !d->gw)) CT_FAIL_ARG("ct_conv2d_backward_weight: null pointer (x / gy / gw)");
-    if (d->ldx < d->Cin || d->ldgy < d->Cout) CT_FAIL_ARG("ct_conv2d_backward_weight: channel pitch below the channel count (x / gy)");
+    const char *fn = "ct_conv2d_backward_weight";
+    if (!d) CT_FAIL_ARG("%s: null descriptor", fn);
+    if (d->ks != 1 && d->ks != 3) CT_FAIL_ARG("%s: ks=%d unsupported (1 or 3)", fn, d->ks);
+    if (d->stride != 1) CT_FAIL_ARG("%s: stride=%d unsupported (1)", fn, d->stride);
+    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) CT_FAIL_ARG("%s: bad shape", fn);
+    if (d->Cin % 16 || d->Cin <= 0) CT_FAIL_ARG("%s: Cin=%d must be a positive multiple of 16", fn, d->Cin);
+    if (needBuffers && (!d->x || !d->gy || !d->gw)) CT_FAIL_ARG("%s: null pointer (x / gy / gw)", fn);
+    if (d->ldx < d->Cin || d->ldgy < d->Cout) CT_FAIL_ARG("%s: channel pitch below the channel count (x / gy)", fn);
     const double px = (double)d->N * d->H * d->W;
     if (px * (d->ldx > d->ldgy ? d->ldx : d->ldgy) * 4.0 >= VIEW_LIMIT)
-        CT_FAIL_ARG("ct_conv2d_backward_weight: a view of 2 GiB or more (N*H*W=%.0f pixels): the kernel addresses every view through one buffer descriptor", px);
-    const int taps = d->ks * d->ks;
-    p->NT = ct_cdiv(d->Cout, 16);
-    p->cgroups = ct_cdiv(d->Cin, 32);
-    const double units = (double)taps * p->cgroups * ct_cdiv(p->NT, 4);
-    if (units > 2147483647.0) CT_FAIL_ARG("ct_conv2d_backward_weight: grid too large");
-    p->units = (int)units;
-    const int nsteps = ct_cdiv(d->N * d->H * d->W, 4);
-    int slabs = ct_cdiv(1024, p->units);
-    const int maxSlabs = ct_cdiv(nsteps, 32);           // at least 8 steps for each of the four waves
-    if (slabs > maxSlabs) slabs = maxSlabs;
-    if (slabs < 1) slabs = 1;
-    p->slabs = slabs;
-    p->stepsPerWave = ct_cdiv(nsteps, slabs * 4);
-    p->slabStride = (size_t)d->Cout * d->Cin * taps + d->Cout;
-    return CT_OK;
+        CT_FAIL_ARG("%s: a view of 2 GiB or more (N*H*W=%.0f pixels): the kernel addresses every view through one buffer descriptor", fn, px);
+    return ct_conv_weight_plan(fn, (int)px, d->Cin, d->Cout, d->ks * d->ks, true, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -390,19 +392,39 @@ extern "C" int ct_conv2d_backward_weight(const ct_conv_bwd_weight_desc *d, void 
                      need, d->workspace ? d->workspace_bytes : (size_t)0);
         return CT_ERR_WORKSPACE;
     }
-    hipStream_t s = (hipStream_t)stream;
     CwArgs a;
     a.x = d->x; a.gy = d->gy; a.ws = d->workspace;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.ldx = d->ldx; a.ldgy = d->ldgy;
-    a.ks = d->ks; a.NT = p.NT; a.cgroups = p.cgroups; a.withBias = d->gb != nullptr;
-    a.stepsPerWave = p.stepsPerWave; a.slabStride = p.slabStride;
-    hipLaunchKernelGGL(conv_bwd_weight_kernel, dim3((unsigned)p.units, (unsigned)p.slabs), dim3(256), 0, s, a);
-    CT_CHECK_LAUNCH("ct_conv2d_backward_weight (weight)");
-    const size_t nw = (size_t)d->Cout * d->Cin * d->ks * d->ks;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((p.slabStride + 255) / 256)), dim3(256), 0, s, d->workspace, p.slabs,
-                       p.slabStride, nw, d->gw, d->gb);
-    CT_CHECK_LAUNCH("ct_conv2d_backward_weight (reduce)");
+    a.N = d->N; a.H = a.Hi = d->H; a.W = a.Wi = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.ldx = d->ldx; a.ldgy = d->ldgy;
+    a.ks = d->ks; a.withBias = d->gb != nullptr;
+    return launch_cw("ct_conv2d_backward_weight", 1, a, p, d->gw, d->gb, (hipStream_t)stream);
+}
+
+int ct_conv_weight_plan(const char *fn, int pixels, int Cin, int Cout, int taps, bool biasTail, CwPlan *p)
+{
+    p->NT = ct_cdiv(Cout, 16);
+    p->cgroups = ct_cdiv(Cin, 32);
+    const double units = (double)taps * p->cgroups * ct_cdiv(p->NT, 4);
+    if (units > 2147483647.0) CT_FAIL_ARG("%s: grid too large", fn);
+    p->units = (int)units;
+    const int nsteps = ct_cdiv(pixels, 4);
+    int slabs = ct_cdiv(1024, p->units);
+    const int maxSlabs = ct_cdiv(nsteps, 32);           // at least 8 steps for each of the four waves
+    if (slabs > maxSlabs) slabs = maxSlabs;
+    if (slabs < 1) slabs = 1;
+    p->slabs = slabs;
+    p->stepsPerWave = ct_cdiv(nsteps, slabs * 4);
+    p->slabStride = (size_t)Cout * Cin * taps + (biasTail ? Cout : 0);
     return CT_OK;
+}
+
+int ct_conv_s2_weight_launch(const ct_conv_s2_bwd_desc *d, const CwPlan &p, void *stream)
+{
+    CwArgs a;
+    a.x = d->x; a.gy = d->gy; a.ws = d->workspace;
+    a.N = d->N; a.H = d->H / 2; a.W = d->W / 2; a.Hi = d->H; a.Wi = d->W;
+    a.Cin = d->Cin; a.Cout = d->Cout; a.ldx = d->ldx; a.ldgy = d->ldgy;
+    a.ks = 3; a.withBias = 0;
+    return launch_cw("ct_conv2d_s2_backward (weight)", 2, a, p, d->gw, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t ct_heads_tail_backward_workspace_bytes(const ct_heads_tail_bwd_desc *d)

@@ -4,7 +4,7 @@
 //     input planes with a 3-pixel zero-padded halo and the weights sit in LDS, an A operand is one LDS read at plane[tab[k] +
 //     pixel]), without the BatchNorm fold: training-mode BatchNorm needs the raw z.  One launch walks the stems present.
 //   * stem_sum_kernel: y = sum_s max(0, fma(z_s - mean_s, a_s, beta_s)), a_s = gamma_s * invstd_s, in the order x, pre_img,
-//     pre_hm; each term is ct_bn_relu_apply's expression (neck_bwd.hip), so the backward's recomputed mask is the forward's.
+//     pre_hm; each term is ct_bn_relu_apply's expression (bn_pre of ct_train.h), so the backward's recomputed mask is the forward's.
 //   * stem_gw_kernel: gw_s[co, j] = sum_p gz_s[p, co] * patch_s[p, j], j = (ci, ky, kx): M = 16 couts, N = 49 Cin columns in
 //     16-column tiles (10 / 4), K = pixels.  A workgroup stages the planes of an 8 x 32 pixel tile (+ halo) in LDS, reads gz as
 //     the A operand straight from the NHWC map, each wave owns two rows of the tile (16 steps of 4 pixels); workgroup b walks the
@@ -14,11 +14,9 @@
 //     (+ halo) and the weights in LDS, one thread per pixel, FMAs in (ky, kx, co) order.  Plain on purpose: training never asks
 //     for an image gradient.
 // Slab counts depend on the shapes only: every result is bitwise equal from run to run.  DESIGN.md section 14.
-#include "ct_common.h"
+#include "ct_train.h"
 
 namespace {
-
-const double VIEW_LIMIT = 2147483648.0;
 
 constexpr int TW = 32, TH = 8;                 // pixel tile of the two MFMA kernels
 constexpr int PW = 40, PH = TH + 6;            // plane pitch 40 (38 used: the k -> k + 1 wrap lands on another bank), rows
@@ -26,8 +24,6 @@ constexpr int PS = PH * PW;                    // floats per plane
 constexpr int GW_SLAB_CAP = 512;               // workgroups per stem of the weight gradient
 constexpr int GT = 16, GP = GT + 6, GLD = 20;  // image gradient: tile, tile + halo, LDS pitch of one pixel's 16 couts
 
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 __host__ __device__ constexpr int cin_of(int s) { return s == 2 ? 1 : 3; }
 
 struct StemTrainArgs {
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(256) void stem_sum_kernel(StemSumArgs a)
             const f32x4 ga = ld4(a.gamma[s] + c), be = ld4(a.beta[s] + c), mean = ld4(a.mean[s] + c), istd = ld4(a.invstd[s] + c);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float t = fmaxf(fmaf(z[i] - mean[i], ga[i] * istd[i], be[i]), 0.0f);      // bn_pre of neck_bwd.hip
+                const float t = fmaxf(bn_pre(z[i], mean[i], ga[i] * istd[i], be[i]), 0.0f);
                 y[i] = s == 0 ? t : y[i] + t;
             }
         }
@@ -308,10 +304,6 @@ __global__ __launch_bounds__(256) void stem_gin_kernel(StemTrainArgs a)
 // ---------------------------------------------------------------------------------------------------------------------
 // host
 
-bool misaligned(const void *p, uintptr_t mask = 15) { return ((uintptr_t)p & mask) != 0; }
-
-#define CT_TRY(e) do { const int rc__ = (e); if (rc__ != CT_OK) return rc__; } while (0)
-
 int check_shape(const char *fn, int N, int H, int W, int maxld)
 {
     if (N <= 0 || H <= 0 || W <= 0) CT_FAIL_ARG("%s: bad shape", fn);
@@ -439,9 +431,7 @@ extern "C" int ct_stem_bn_relu_sum(const ct_stem_sum_desc *d, void *stream)
         }
     }
     a.y = d->y; a.ldy = d->ldy; a.P = d->N * d->H * d->W;
-    const int total = a.P * 4;
-    const unsigned grid = (unsigned)(total < 2048 * 256 ? ct_cdiv(total, 256) : 2048);
-    hipLaunchKernelGGL(stem_sum_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stem_sum_kernel, dim3(ew_grid(a.P * 4)), dim3(256), 0, (hipStream_t)stream, a);
     CT_CHECK_LAUNCH(fn);
     return CT_OK;
 }
@@ -462,11 +452,7 @@ extern "C" int ct_stem_conv_backward(const ct_stem_conv_desc *d, void *stream)
     int ngw, ngin;
     size_t wsf;
     CT_TRY(make_bwd_plan(fn, d, &a, &ngw, &ngin, &wsf));
-    if (ngw && (!d->workspace || d->workspace_bytes < wsf * sizeof(float) || misaligned(d->workspace))) {
-        ct_set_error("%s: a 16-byte aligned workspace of %zu bytes needed (ct_stem_conv_backward_workspace_bytes), got %zu", fn,
-                     wsf * sizeof(float), d->workspace ? d->workspace_bytes : (size_t)0);
-        return CT_ERR_WORKSPACE;
-    }
+    if (ngw) CT_TRY(check_workspace(fn, "ct_stem_conv_backward_workspace_bytes", d->workspace, d->workspace_bytes, wsf * sizeof(float)));
     a.ws = d->workspace;
     hipStream_t st = (hipStream_t)stream;
     if (ngw) {

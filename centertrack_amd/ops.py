@@ -293,10 +293,12 @@ def make_loss_desc(heads, grads=None):
     return d, arr
 
 
-def _loss_workspace(lib, d, dev):
-    need = lib.ct_generic_loss_workspace_bytes(ctypes.byref(d))
+def _workspace(lib, query_name, d, dev):
+    """Allocate what ``query_name`` (a ``ct_*_workspace_bytes``) asks for the descriptor ``d`` and hand it to ``d``; 0 bytes is
+    a rejected descriptor.  The caller keeps the returned tensor alive over its launch."""
+    need = getattr(lib, query_name)(ctypes.byref(d))
     if not need:
-        raise _lib.CTError('ct_generic_loss_workspace_bytes: %s' % lib.ct_last_error().decode())
+        raise _lib.CTError('%s: %s' % (query_name, lib.ct_last_error().decode()))
     ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
     d.workspace, d.workspace_bytes = ws.data_ptr(), need
     return ws
@@ -308,7 +310,7 @@ def generic_loss_forward(heads):
     d, _keep = make_loss_desc(heads)
     dev = heads[0][1].device
     loss = torch.empty(len(heads), dtype=torch.float32, device=dev)
-    _ws = _loss_workspace(lib, d, dev)
+    _ws = _workspace(lib, 'ct_generic_loss_workspace_bytes', d, dev)
     d.loss = loss.data_ptr()
     _lib.check(lib.ct_generic_loss_forward(ctypes.byref(d), _lib.stream_ptr()), 'ct_generic_loss_forward')
     return loss
@@ -327,7 +329,7 @@ def generic_loss_backward(heads, grad_loss, needs=None):
     grad_loss = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
     if grad_loss.numel() != len(heads):
         raise _lib.CTError('generic_loss_backward: grad_loss has %d elements for %d heads' % (grad_loss.numel(), len(heads)))
-    _ws = _loss_workspace(lib, d, dev)
+    _ws = _workspace(lib, 'ct_generic_loss_workspace_bytes', d, dev)
     d.grad_loss = grad_loss.data_ptr()
     _lib.check(lib.ct_generic_loss_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_generic_loss_backward')
     return grads
@@ -344,14 +346,10 @@ def conv_backward_weight(x, gy, ks, need_bias=True):
     d.x, d.N, d.H, d.W, d.Cin, d.ldx = x.ptr, x.N, x.H, x.W, x.C, x.ld
     d.gy, d.Cout, d.ldgy = gy.ptr, gy.C, gy.ld
     d.ks, d.stride = ks, 1
-    need = lib.ct_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))
-    if not need:
-        raise _lib.CTError('ct_conv2d_backward_weight_workspace_bytes: %s' % lib.ct_last_error().decode())
+    _ws = _workspace(lib, 'ct_conv2d_backward_weight_workspace_bytes', d, dev)
     gw = torch.empty((gy.C, x.C, ks, ks), dtype=torch.float32, device=dev)
     gb = torch.empty(gy.C, dtype=torch.float32, device=dev) if need_bias else None
-    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
     d.gw, d.gb = gw.data_ptr(), _p(gb)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), need
     _lib.check(lib.ct_conv2d_backward_weight(ctypes.byref(d), _lib.stream_ptr()), 'ct_conv2d_backward_weight')
     return gw, gb
 
@@ -461,12 +459,8 @@ def heads_backward(feat, mid, gouts, w0, w2s, needs, gmid=None):
         gmid = None
     d, _keep = make_heads_tail_desc(mid, g, w2, gmid, gw2, gb2)
     if d.flags:
-        need = lib.ct_heads_tail_backward_workspace_bytes(ctypes.byref(d))
         if d.flags & _lib.CT_HEADS_BWD_WEIGHT:
-            if not need:
-                raise _lib.CTError('ct_heads_tail_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
-            ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-            d.workspace, d.workspace_bytes = ws.data_ptr(), need
+            _ws = _workspace(lib, 'ct_heads_tail_backward_workspace_bytes', d, dev)
         _lib.check(lib.ct_heads_tail_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_heads_tail_backward')
     res['w2'], res['b2'], res['gmid'] = dict(zip(heads, gw2)), dict(zip(heads, gb2)), gmid
     if need_w0 or need_b0:
@@ -514,26 +508,46 @@ def upsample_add(x, w, f, skip, out=None):
     return out
 
 
-def _bn_desc(z, mean=None, invstd=None, gamma=None, beta=None):
-    d = _lib.BnDesc()
-    d.z, d.N, d.H, d.W, d.C, d.ldz = z.ptr, z.N, z.H, z.W, z.C, z.ld
-    d.mean, d.invstd, d.gamma, d.beta = _p(mean), _p(invstd), _p(gamma), _p(beta)
-    return d
-
-
-def _bn_workspace(lib, d, dev):
-    need = lib.ct_bn_workspace_bytes(ctypes.byref(d))
-    if not need:
-        raise _lib.CTError('ct_bn_workspace_bytes: %s' % lib.ct_last_error().decode())
-    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), need
-    return ws
-
-
 def _bn_vec(t, C, what):
     if t.numel() != C or t.dtype != torch.float32 or not t.is_contiguous() or t.device != what.buf.device:
         raise _lib.CTError('batch norm: a per-channel vector must be contiguous fp32 [%d] on %s' % (C, what.buf.device))
     return t
+
+
+def _bn_desc(cls, z, mean, invstd, gamma=None, beta=None, flags=0):
+    """a ``ct_bn_desc`` (``_lib.BnDesc``) or ``ct_bn_act_desc`` (``_lib.BnActDesc``) over the map ``z``: the fields the two share"""
+    d = cls()
+    d.z, d.N, d.H, d.W, d.C, d.ldz = z.ptr, z.N, z.H, z.W, z.C, z.ld
+    d.mean, d.invstd, d.gamma, d.beta = (None if t is None else _bn_vec(t, z.C, z).data_ptr() for t in (mean, invstd, gamma, beta))
+    d.flags = flags
+    return d
+
+
+def _bn_apply(entry, d, z, out):
+    if out is None:
+        out = new_view(z.N, z.H, z.W, z.C, z.buf.device)
+    d.y, d.ldy = out.ptr, out.ld
+    _lib.check(getattr(_lib.load(), entry)(ctypes.byref(d), _lib.stream_ptr()), entry)
+    return out
+
+
+def _bn_backward(entry, query_name, d, z, gy, need_z, need_gamma, need_beta):
+    """``gy``, the outputs asked for and, where the call sums, the workspace into ``d``; the call -> (gz, ggamma, gbeta)"""
+    lib = _lib.load()
+    dev = z.buf.device
+    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
+        raise _lib.CTError('%s: gy does not have the shape of z' % entry[3:])
+    d.gy, d.ldgy = gy.ptr, gy.ld
+    gz = new_view(z.N, z.H, z.W, z.C, dev) if need_z else None
+    gg = torch.empty(z.C, dtype=torch.float32, device=dev) if need_gamma else None
+    gb = torch.empty(z.C, dtype=torch.float32, device=dev) if need_beta else None
+    if gz is not None:
+        d.gz, d.ldgz = gz.ptr, gz.ld
+    d.ggamma, d.gbeta = _p(gg), _p(gb)
+    if need_gamma or need_beta or (need_z and d.flags & _lib.CT_BN_BATCH_STATS):
+        _ws = _workspace(lib, query_name, d, dev)
+    _lib.check(getattr(lib, entry)(ctypes.byref(d), _lib.stream_ptr()), entry)
+    return gz, gg, gb
 
 
 def bn_stats(z, eps=1e-5):
@@ -542,46 +556,25 @@ def bn_stats(z, eps=1e-5):
     lib = _lib.load()
     dev = z.buf.device
     mean, var, invstd = (torch.empty(z.C, dtype=torch.float32, device=dev) for _ in range(3))
-    d = _bn_desc(z, mean, invstd)
+    d = _bn_desc(_lib.BnDesc, z, mean, invstd)
     d.var, d.eps = var.data_ptr(), eps
-    _ws = _bn_workspace(lib, d, dev)
+    _ws = _workspace(lib, 'ct_bn_workspace_bytes', d, dev)
     _lib.check(lib.ct_bn_stats(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_stats')
     return mean, var, invstd
 
 
 def bn_relu_apply(z, mean, invstd, gamma, beta, out=None):
     """y = max(0, fma(z - mean, a, beta)), a = gamma * invstd on NHWC views; allocates ``out`` if not given."""
-    lib = _lib.load()
-    if out is None:
-        out = new_view(z.N, z.H, z.W, z.C, z.buf.device)
-    d = _bn_desc(z, *(_bn_vec(t, z.C, z) for t in (mean, invstd, gamma, beta)))
-    d.y, d.ldy = out.ptr, out.ld
-    _lib.check(lib.ct_bn_relu_apply(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_relu_apply')
-    return out
+    return _bn_apply('ct_bn_relu_apply', _bn_desc(_lib.BnDesc, z, mean, invstd, gamma, beta), z, out)
 
 
 def bn_relu_backward(z, gy, mean, invstd, gamma, beta, batch_stats, need_z=True, need_gamma=True, need_beta=True):
     """Gradients of ``bn_relu_apply`` (with ``batch_stats``: through the batch statistics as well) for the output gradient
     ``gy`` -> ``(gz view, ggamma, gbeta)``, None for what was not asked for.  Bitwise reproducible."""
-    lib = _lib.load()
-    dev = z.buf.device
     if not (need_z or need_gamma or need_beta):
         return None, None, None
-    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
-        raise _lib.CTError('bn_relu_backward: gy does not have the shape of z')
-    d = _bn_desc(z, *(_bn_vec(t, z.C, z) for t in (mean, invstd, gamma, beta)))
-    d.gy, d.ldgy = gy.ptr, gy.ld
-    gz = new_view(z.N, z.H, z.W, z.C, dev) if need_z else None
-    gg = torch.empty(z.C, dtype=torch.float32, device=dev) if need_gamma else None
-    gb = torch.empty(z.C, dtype=torch.float32, device=dev) if need_beta else None
-    if gz is not None:
-        d.gz, d.ldgz = gz.ptr, gz.ld
-    d.ggamma, d.gbeta = _p(gg), _p(gb)
-    d.flags = _lib.CT_BN_BATCH_STATS if batch_stats else 0
-    if need_gamma or need_beta or batch_stats:
-        _ws = _bn_workspace(lib, d, dev)
-    _lib.check(lib.ct_bn_relu_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_relu_backward')
-    return gz, gg, gb
+    d = _bn_desc(_lib.BnDesc, z, mean, invstd, gamma, beta, _lib.CT_BN_BATCH_STATS if batch_stats else 0)
+    return _bn_backward('ct_bn_relu_backward', 'ct_bn_workspace_bytes', d, z, gy, need_z, need_gamma, need_beta)
 
 
 def upsample_add_backward(x, w, f, gy, need_x=True, need_w=True):
@@ -607,11 +600,7 @@ def upsample_add_backward(x, w, f, gy, need_x=True, need_w=True):
     if need_w:
         gw = torch.empty((gy.C, 1, 2 * f, 2 * f), dtype=torch.float32, device=dev)
         d.x, d.ldx, d.gw = x.ptr, x.ld, gw.data_ptr()
-        need = lib.ct_upsample_add_backward_workspace_bytes(ctypes.byref(d))
-        if not need:
-            raise _lib.CTError('ct_upsample_add_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+        _ws = _workspace(lib, 'ct_upsample_add_backward_workspace_bytes', d, dev)
     _lib.check(lib.ct_upsample_add_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_upsample_add_backward')
     return gx, gw, gy
 
@@ -654,7 +643,7 @@ def conv_s2_backward(x, gy, w=None, need_x=True, need_w=True, gx=None):
     d = _lib.ConvS2BwdDesc()
     d.x, d.N, d.H, d.W, d.Cin, d.ldx = x.ptr, x.N, x.H, x.W, x.C, x.ld
     d.gy, d.Cout, d.ldgy = gy.ptr, gy.C, gy.ld
-    gw = wp = ws = None
+    gw = wp = None
     if need_x:
         if w is None:
             raise _lib.CTError('conv_s2_backward: the input gradient needs the weight')
@@ -665,38 +654,27 @@ def conv_s2_backward(x, gy, w=None, need_x=True, need_w=True, gx=None):
     else:
         gx = None
     if need_w:
-        need = lib.ct_conv2d_s2_backward_workspace_bytes(ctypes.byref(d))
-        if not need:
-            raise _lib.CTError('ct_conv2d_s2_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
+        _ws = _workspace(lib, 'ct_conv2d_s2_backward_workspace_bytes', d, dev)
         gw = torch.empty((gy.C, x.C, 3, 3), dtype=torch.float32, device=dev)
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        d.gw, d.workspace, d.workspace_bytes = gw.data_ptr(), ws.data_ptr(), need
+        d.gw = gw.data_ptr()
     _lib.check(lib.ct_conv2d_s2_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_conv2d_s2_backward')
     return gx, gw
 
 
 def _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, batch_stats=False):
-    d = _lib.BnActDesc()
-    d.z, d.N, d.H, d.W, d.C, d.ldz = z.ptr, z.N, z.H, z.W, z.C, z.ld
-    d.mean, d.invstd, d.gamma, d.beta = (_bn_vec(t, z.C, z).data_ptr() for t in (mean, invstd, gamma, beta))
+    d = _bn_desc(_lib.BnActDesc, z, mean, invstd, gamma, beta,
+                 (_lib.CT_BN_ACT_RELU if relu else 0) | (_lib.CT_BN_BATCH_STATS if batch_stats else 0))
     if res is not None:
         if (res.N, res.H, res.W, res.C) != (z.N, z.H, z.W, z.C):
             raise _lib.CTError('batch norm: the residual does not have the shape of z')
         d.res, d.ldr = res.ptr, res.ld
-    d.flags = (_lib.CT_BN_ACT_RELU if relu else 0) | (_lib.CT_BN_BATCH_STATS if batch_stats else 0)
     return d
 
 
 def bn_act_apply(z, mean, invstd, gamma, beta, res=None, relu=True, out=None):
     """y = fma(z - mean, a, beta) (+ res) (max 0), a = gamma * invstd on NHWC views; allocates ``out`` if not
     given."""
-    lib = _lib.load()
-    if out is None:
-        out = new_view(z.N, z.H, z.W, z.C, z.buf.device)
-    d = _bn_act_desc(z, mean, invstd, gamma, beta, res, relu)
-    d.y, d.ldy = out.ptr, out.ld
-    _lib.check(lib.ct_bn_act_apply(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_act_apply')
-    return out
+    return _bn_apply('ct_bn_act_apply', _bn_act_desc(z, mean, invstd, gamma, beta, res, relu), z, out)
 
 
 def bn_act_backward(z, gy, mean, invstd, gamma, beta, batch_stats, res=None, relu=True, need_z=True, need_res=False,
@@ -704,30 +682,13 @@ def bn_act_backward(z, gy, mean, invstd, gamma, beta, batch_stats, res=None, rel
     """Gradients of ``bn_act_apply`` (with ``batch_stats``: through the batch statistics as well) for the output gradient
     ``gy`` -> ``(gz view, gres view, ggamma, gbeta)``, None for what was not asked for.  ``res``: the forward's residual (it
     decides the ReLU mask).  Bitwise reproducible."""
-    lib = _lib.load()
-    dev = z.buf.device
     if not (need_z or need_res or need_gamma or need_beta):
         return None, None, None, None
-    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
-        raise _lib.CTError('bn_act_backward: gy does not have the shape of z')
     d = _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, batch_stats)
-    d.gy, d.ldgy = gy.ptr, gy.ld
-    gz = new_view(z.N, z.H, z.W, z.C, dev) if need_z else None
-    gr = new_view(z.N, z.H, z.W, z.C, dev) if need_res else None
-    gg = torch.empty(z.C, dtype=torch.float32, device=dev) if need_gamma else None
-    gb = torch.empty(z.C, dtype=torch.float32, device=dev) if need_beta else None
-    if gz is not None:
-        d.gz, d.ldgz = gz.ptr, gz.ld
+    gr = new_view(z.N, z.H, z.W, z.C, z.buf.device) if need_res else None
     if gr is not None:
         d.gres, d.ldgres = gr.ptr, gr.ld
-    d.ggamma, d.gbeta = _p(gg), _p(gb)
-    if need_gamma or need_beta or (batch_stats and need_z):
-        need = lib.ct_bn_act_workspace_bytes(ctypes.byref(d))
-        if not need:
-            raise _lib.CTError('ct_bn_act_workspace_bytes: %s' % lib.ct_last_error().decode())
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), need
-    _lib.check(lib.ct_bn_act_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_act_backward')
+    gz, gg, gb = _bn_backward('ct_bn_act_backward', 'ct_bn_act_workspace_bytes', d, z, gy, need_z, need_gamma, need_beta)
     return gz, gr, gg, gb
 
 
@@ -851,11 +812,7 @@ def stem_conv_backward(gzs, inputs=(None, None, None), weights=(None, None, None
                       else torch.empty((N, STEM_CIN[s], H, W), dtype=torch.float32, device=dev))
             d.gin[s] = gin[s].data_ptr()
     if any(g is not None for g in gw):
-        need = lib.ct_stem_conv_backward_workspace_bytes(ctypes.byref(d))
-        if not need:
-            raise _lib.CTError('ct_stem_conv_backward_workspace_bytes: %s' % lib.ct_last_error().decode())
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+        _ws = _workspace(lib, 'ct_stem_conv_backward_workspace_bytes', d, dev)
     _lib.check(lib.ct_stem_conv_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_stem_conv_backward')
     return gw, gin
 

@@ -445,7 +445,7 @@ int ct_pack_conv_weight_s2t(const float *w_oihw, float *packed, int Cout, int Ci
  *                        ReLU; gres = g; gbeta, ggamma, gz from g as in ct_bn_relu_backward (CT_BN_BATCH_STATS: through the
  *                        batch statistics).  gz, gres, ggamma, gbeta may each be NULL (not computed).
  *   mean / invstd are what the forward used (ct_bn_stats on a ct_bn_desc of the same map, or the running statistics).  With the
- *   ReLU and no residual y and gz equal ct_bn_relu_apply / _backward bit for bit.  The backward needs
+ *   ReLU and no residual these are ct_bn_relu_apply / _backward (which widen their ct_bn_desc and run the same code).  The backward needs
  *   ct_bn_act_workspace_bytes(d) bytes (0 for a rejected descriptor) whenever it sums: for ggamma, gbeta or a batch-statistics
  *   gz.  var and eps are not read. */
 #define CT_BN_ACT_RELU 2

@@ -1,7 +1,8 @@
 """Shared pieces of the trainable-backbone tests (tests/test_backbone_backward_cpu.py, tests/test_hip_backbone_backward.py):
 the reference construction of BasicBlock / Root / Tree / DLA (dla.py:38-66,154-316) restated on torch functions (``F.conv2d``,
 ``F.batch_norm``, ``F.max_pool2d``) for any dtype over a state dict, the stride-2 input gradient and the pool's tie rule as
-explicit sums, and the slab / workspace formulas of centertrack_amd/csrc/backbone_bwd.hip.  No GPU, no ctypes.
+explicit sums, and the slab / workspace formulas of centertrack_amd/csrc/backbone_bwd.hip (the BatchNorm plan, bn_train.hip's,
+comes from tests/_neck_bwd.py).  No GPU, no ctypes.
 
 A construction run takes a ``Tape``.  Empty, the run is free: every ReLU and every pool decides by its own values.  Filled
 with the maps ``centertrack_amd.dla_base.trace`` received from a HIP forward (moved to the CPU, NCHW), every ReLU becomes a
@@ -44,9 +45,9 @@ POOL_PLAN_SHAPES = [(3, 256, 260, 44)]
 # the launch plans, restated
 
 def s2_plan(N, H, W, Cin, Cout):
-    """make_s2_plan: the input gradient runs one workgroup per (image, 4 x 16 cells, 32 input channels); the weight gradient
+    """make_s2_plan (its weight half is ct_conv_weight_plan of heads_bwd.hip): the input gradient runs one workgroup per (image, 4 x 16 cells, 32 input channels); the weight gradient
     one per (tap, 32 input channels, 64 couts) and K slab of output pixels; workspace = slabs * Cout * Cin * 9 floats.
-    ``wanted`` = the grid target, ``maxSlabs`` = the pixel limit; then what follows inside conv_s2_gw_kernel (wave j of the
+    ``wanted`` = the grid target, ``maxSlabs`` = the pixel limit; then what follows inside conv_bwd_weight_kernel<2> (wave j of the
     slabs * 4 runs steps j * stepsPerWave .. of ``nsteps``: the waves and slabs past the end are idle) and conv_s2_gx_kernel."""
     Ho, Wo = H // 2, W // 2
     cgroups = cdiv(Cin, 32)

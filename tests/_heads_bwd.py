@@ -113,7 +113,7 @@ def terms(case):
 # the host plans, restated
 
 def cw_plan(N, H, W, Cin, Cout, ks):
-    """make_cw_plan of heads_bwd.hip; ``slabs`` is observable through ct_conv2d_backward_weight_workspace_bytes"""
+    """make_cw_plan / ct_conv_weight_plan of heads_bwd.hip (with the bias tail); ``slabs`` is observable through ct_conv2d_backward_weight_workspace_bytes"""
     taps = ks * ks
     NT = cdiv(Cout, 16)
     units = taps * cdiv(Cin, 32) * cdiv(NT, 4)

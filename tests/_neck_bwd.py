@@ -1,7 +1,8 @@
 """Shared pieces of the trainable-neck tests (tests/test_neck_backward_cpu.py, tests/test_hip_neck_backward.py): the
 reference construction of DeformConv / IDAUp / DLAUp restated on torch functions (``oracle.dcn_v2.dcn_forward``,
 ``F.batch_norm``, ``F.conv_transpose2d(groups = C)``) for any dtype, the up-sampling backward as the explicit sums, the
-designed offset parameters, and the slab / workspace formulas of centertrack_amd/csrc/neck_bwd.hip.  No GPU, no ctypes."""
+designed offset parameters, and the slab / workspace formulas of centertrack_amd/csrc/bn_train.hip (BatchNorm) and
+centertrack_amd/csrc/neck_bwd.hip (up-sampling).  No GPU, no ctypes."""
 import math
 from collections import OrderedDict
 
@@ -17,7 +18,7 @@ BUFFERS = ('running_mean', 'running_var', 'num_batches_tracked')
 # ---------------------------------------------------------------------------------------------------------------------
 # the launch plans, restated
 
-# ``ew_grid`` of neck_bwd.hip / backbone_bwd.hip launches cdiv(total, 256) workgroups of 256 threads below this many channel
+# ``ew_grid`` of ct_train.h launches cdiv(total, 256) workgroups of 256 threads below this many channel
 # quads and 2048 from there on, where the grid-stride loop of the element-wise kernels runs a second time.  The constant is
 # not observable through the ABI: it is mirrored by reading.
 EW_CAP = 2048 * 256
@@ -31,8 +32,8 @@ def ew_plan(quads):
 
 
 def bn_plan(N, H, W, C):
-    """make_bn_plan (neck_bwd.hip; make_bn_act_plan of backbone_bwd.hip is the same arithmetic): slabs of pixels x chunks of up
-    to 64 channel quads; workspace = (slabs + 1) * 2 * C floats.  ``wanted`` = the grid target, ``maxSlabs`` = the pixel limit;
+    """make_bn_plan of bn_train.hip (the one plan of ct_bn_* and ct_bn_act_*): slabs of pixels x chunks of up to 64 channel
+    quads; workspace = (slabs + 1) * 2 * C floats.  ``wanted`` = the grid target, ``maxSlabs`` = the pixel limit;
     the element-wise kernels (apply, backward) run over P * C / 4 quads (``ew_plan``)."""
     P, C4 = N * H * W, C // 4
     cw = min(C4, 64)

@@ -1,4 +1,4 @@
-"""CPU: the host side of the trainable backbone (centertrack_amd/csrc/backbone_bwd.hip, centertrack_amd/dla_base.py) -- exports
+"""CPU: the host side of the trainable backbone (centertrack_amd/csrc/backbone_bwd.hip, centertrack_amd/csrc/bn_train.hip, centertrack_amd/dla_base.py) -- exports
 and descriptor layouts, argument validation and workspace queries of the stride-2 convolution backward, BatchNorm-act and
 max-pool-backward entry points, the restated plans against those queries, the names, shapes and initialisation of the drop-in
 modules, what they refuse, the parity decomposition and the pool's tie rule as explicit float64 sums against autograd, and the

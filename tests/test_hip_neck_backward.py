@@ -1,4 +1,4 @@
-"""GPU: the trainable neck (centertrack_amd/csrc/neck_bwd.hip, centertrack_amd/dla_up.py) against float64 torch autograd on
+"""GPU: the trainable neck (centertrack_amd/csrc/bn_train.hip, centertrack_amd/csrc/neck_bwd.hip, centertrack_amd/dla_up.py) against float64 torch autograd on
 the CPU of the restated reference construction (tests/_neck_bwd.py).  Error measure and bound are the project's
 (tests/_dcn_bwd.py): ``err`` relative to the tensor's maximum, ``bound(e32, K) = min(1e-3, 4 max(e32, 2^-23 sqrt(K)))`` with
 e32 the float32 CPU run of the same construction.  K = N*H*W for the BatchNorm gradients, the up-sampling weight gradient and

@@ -1,4 +1,4 @@
-"""CPU: the host side of the trainable neck (centertrack_amd/csrc/neck_bwd.hip, centertrack_amd/dla_up.py) -- exports and
+"""CPU: the host side of the trainable neck (centertrack_amd/csrc/bn_train.hip, centertrack_amd/csrc/neck_bwd.hip, centertrack_amd/dla_up.py) -- exports and
 descriptor layouts, argument validation and workspace queries of the BatchNorm, up-sampling-backward and mask-sigmoid entry
 points, the restated slab plans against those queries, the names, shapes and initialisation of DeformConv / IDAUp / DLAUp, and
 the float64 helper's up-sampling formula against autograd.  Nothing here launches a kernel."""

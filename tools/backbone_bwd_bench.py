@@ -186,7 +186,7 @@ class ChildFailed(Exception):
     """the traced child ended badly (non-zero exit, a signal, the time limit): nothing more is started on the GPU"""
 
 
-NEW_KERNELS = ('conv_s2_gx_kernel', 'conv_s2_gw_kernel', 's2_slab_reduce_kernel', 'pack_s2t_kernel', 'bn_act_', 'maxpool_bwd_kernel')
+NEW_KERNELS = ('conv_s2_gx_kernel', 'conv_bwd_weight_kernel<2>', 'pack_s2t_kernel', 'bn_act_', 'maxpool_bwd_kernel')
 
 
 def count_launches(name, steps, timeout):
