@@ -731,6 +731,19 @@ extern "C" size_t ct_conv2d_workspace_bytes(const ct_conv_desc *d)
 
 int ct_conv2d_winograd(const ct_conv_desc *d, void *stream);       // wino_mfma.hip
 
+// Every NHWC view of a launch against ct_check_image_view (ct_common.h): x, y, res and the two side outputs of the 3x3 stride-2
+// shapes.  An NCHW output is addressed with size_t and has no limit.  (Ho, Wo): the output grid.
+int ct_conv2d_check_views(const ct_conv_desc *d, int Ho, int Wo)
+{
+    const char *fn = "ct_conv2d";
+    int rc = ct_check_image_view(fn, "x", d->H, d->W, d->ldx, d->Cin);
+    if (rc == CT_OK && !(d->flags & CT_OUT_NCHW)) rc = ct_check_image_view(fn, "y", Ho, Wo, d->ldy, d->Cout);
+    if (rc == CT_OK && d->res) rc = ct_check_image_view(fn, "res", Ho, Wo, d->ldr, d->Cout);
+    if (rc == CT_OK && d->pool_y) rc = ct_check_image_view(fn, "pool_y", d->H / 2, d->W / 2, d->pool_ld, d->Cin);
+    if (rc == CT_OK && d->proj_w_packed && d->proj_y) rc = ct_check_image_view(fn, "proj_y", Ho, Wo, d->proj_ldy, d->Cout);
+    return rc;
+}
+
 extern "C" int ct_conv2d(const ct_conv_desc *d, void *stream)
 {
     if (d && d->algo >= 201 && d->algo <= 211) {
@@ -740,6 +753,8 @@ extern "C" int ct_conv2d(const ct_conv_desc *d, void *stream)
     }
     Plan p;
     int rc = make_plan(d, &p);
+    if (rc != CT_OK) return rc;
+    rc = ct_conv2d_check_views(d, p.Ho, p.Wo);
     if (rc != CT_OK) return rc;
     const size_t need = ws_bytes(d, p);
     if (need > 0 && (!d->workspace || d->workspace_bytes < need)) {

@@ -27,6 +27,21 @@ void ct_set_error(const char *fmt, ...);
 
 static inline int ct_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// a view is addressed with 32-bit element offsets or through one buffer descriptor (31-bit byte offsets): it stays below 2 GiB
+static const double VIEW_LIMIT = 2147483648.0;
+
+// An NHWC view the forward convolutions put behind one buffer descriptor PER IMAGE (conv_mfma.hip, ksplit_core.h, wino_mfma.hip,
+// ct_store_tile): the pitch holds the channels, and the image's extent ((H*W - 1) * ld + C) * 4 bytes stays below 2 GiB -- the
+// descriptors cast it to int, the byte offsets are int and 0x80000000 must stay out of range.
+static inline int ct_check_image_view(const char *fn, const char *name, int H, int W, int ld, int C)
+{
+    if (ld < C) CT_FAIL_ARG("%s: channel pitch of %s (%d) below the channel count %d", fn, name, ld, C);
+    if ((((double)H * W - 1.0) * ld + C) * 4.0 >= VIEW_LIMIT)
+        CT_FAIL_ARG("%s: a view of 2 GiB or more per image (%s: %dx%d pixels at pitch %d): the kernels address an image with 32-bit offsets",
+                    fn, name, H, W, ld);
+    return CT_OK;
+}
+
 // tuning knobs (ct_set_tuning); defaults chosen from MI355X measurements, see DESIGN.md
 enum { CT_TUNE_CONV_CFG = 0, CT_TUNE_CONV_PIPE, CT_TUNE_CONV_SMALL_TILES, CT_TUNE_SPLITK_TARGET, CT_TUNE_DCN_BN,
        CT_TUNE_CONV_KS, CT_TUNE_CONV_KS_BELOW, CT_TUNE_CONV_KS_WAVES, CT_TUNE_XCD_REMAP, CT_TUNE_HEADS_ORDER, CT_TUNE_STEM_ROWS, CT_TUNE_DCN_SLOTS, CT_TUNE_DCN_XCD, CT_TUNE_COUNT };

@@ -30,8 +30,7 @@ __device__ __forceinline__ float bn_pre(float z, float mean, float a, float beta
 
 // ---- host
 
-// a view is addressed with 32-bit element offsets or through one buffer descriptor (31-bit byte offsets): it stays below 2 GiB
-static const double VIEW_LIMIT = 2147483648.0;
+// (VIEW_LIMIT, the 2 GiB bound of a view: ct_common.h)
 
 #define CT_TRY(e) do { const int rc__ = (e); if (rc__ != CT_OK) return rc__; } while (0)
 

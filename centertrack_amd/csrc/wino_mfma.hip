@@ -650,6 +650,8 @@ extern "C" int ct_pack_winograd_weight(const float *w_oihw, float *packed, int C
     return CT_OK;
 }
 
+int ct_conv2d_check_views(const ct_conv_desc *d, int Ho, int Wo);      // conv_mfma.hip
+
 // called by ct_conv2d for algo 201..207
 int ct_conv2d_winograd(const ct_conv_desc *d, void *stream)
 {
@@ -658,6 +660,11 @@ int ct_conv2d_winograd(const ct_conv_desc *d, void *stream)
     if (d->Cin % 64) CT_FAIL_ARG("ct_conv2d: the Winograd algo needs Cin %% 64 == 0 (got %d)", d->Cin);
     if (d->flags & CT_OUT_NCHW) CT_FAIL_ARG("ct_conv2d: the Winograd algo writes NHWC only");
     if (d->sig_hi > d->sig_lo || d->dep_hi > d->dep_lo) CT_FAIL_ARG("ct_conv2d: the Winograd algo has no sigmoid epilogue");
+    if (d->Cout <= 0 || d->N <= 0 || d->H <= 0 || d->W <= 0) CT_FAIL_ARG("ct_conv2d: bad shape");
+    {
+        const int rc = ct_conv2d_check_views(d, d->H, d->W);
+        if (rc != CT_OK) return rc;
+    }
     // algo 201: 64 px x 64 couts, 202: 64 x 32, 203: 128 x 32, 204: 128 x 16 per workgroup of 4 waves;
     // 205 / 206: 64 x 32 with K split over 2 / 4 wave groups (8 / 16 waves), 207: 64 x 16 with K split 4;
     // 208..211: 64 x 32 walking 2 / 4 / 5 / 8 cout blocks per workgroup on one input transform (Cin == 64 only)
