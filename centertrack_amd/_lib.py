@@ -284,6 +284,18 @@ class FrameStepArgs(ctypes.Structure):
 CT_FRAME_DEVICE, CT_FRAME_HOST, CT_FRAME_IN_PLACE, CT_FRAME_UPLOADED = range(4)
 
 
+CT_TARGETS_CULL_CAP = 256
+CT_TARGETS_MAX_OUT = 32
+
+
+class TargetsDesc(ctypes.Structure):
+    _fields_ = [('staging_host', ctypes.c_void_p), ('staging_dev', ctypes.c_void_p), ('words', ctypes.c_size_t),
+                ('B', ctypes.c_int), ('C', ctypes.c_int), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('max_objs', ctypes.c_int), ('slot_words', ctypes.c_int), ('nout', ctypes.c_int),
+                ('hm', ctypes.c_void_p), ('pre_hm', ctypes.c_void_p)]
+
+
 ABI_VERSION = 103       # CT_ABI_VERSION of include/centertrack_hip.h
 
 EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_elems', 'ct_pack_conv_weight',
@@ -307,7 +319,8 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_memcpy_async', 'ct_memset_async', 'ct_stream_synchronize', 'ct_flip_merge', 'ct_flip_images',
            'ct_frame_loop_create', 'ct_frame_loop_destroy', 'ct_frame_loop_submit', 'ct_frame_loop_wait', 'ct_frame_loop_finish',
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
-           'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host']
+           'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
+           'ct_build_targets', 'ct_build_targets_header_words']
 
 _lib = None
 
@@ -457,6 +470,9 @@ def load():
     lib.ct_frame_loop_in_flight.argtypes = [p]
     lib.ct_frame_loop_forget_upload.restype = None
     lib.ct_frame_loop_forget_upload.argtypes = [p]
+    lib.ct_build_targets_header_words.restype = sz
+    lib.ct_build_targets_header_words.argtypes = [i, i, i, i]
+    lib.ct_build_targets.argtypes = [ctypes.POINTER(TargetsDesc), p]
     # CENTERTRACK_TUNE="key=value,key=value": launch-heuristic knobs of ct_set_tuning (A/B runs)
     for kv in filter(None, os.environ.get('CENTERTRACK_TUNE', '').split(',')):
         k, _, v = kv.partition('=')

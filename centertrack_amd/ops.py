@@ -964,3 +964,20 @@ class Decoder(object):
             ret[name] = v[..., 0] if name in ('scores', 'clses', 'xs', 'ys', 'kps_score') else v
         ret['cts'] = packed[..., 2:4]
         return ret
+
+
+def build_targets(staging_host, staging_dev, words, B, max_objs, slot_words, nout, hm=None, pre_hm=None):
+    """ct_build_targets (csrc/targets.hip) on the current stream: upload ``words`` int32 words of the packed batch from the
+    pinned ``staging_host`` to ``staging_dev`` and write hm [B,C,h,w], pre_hm [B,1,H,W] (either may be None) and the slot
+    tensors the buffer's output table names, in one launch.  ``centertrack_amd.targets.TargetBuilder.render`` packs the
+    buffer; bad contents raise ``CTError`` before anything is enqueued."""
+    d = _lib.TargetsDesc()
+    d.staging_host, d.staging_dev, d.words = staging_host.data_ptr(), staging_dev.data_ptr(), words
+    d.B, d.max_objs, d.slot_words, d.nout = B, max_objs, slot_words, nout
+    if hm is not None:
+        d.hm = hm.data_ptr()
+        _, d.C, d.h, d.w = hm.shape
+    if pre_hm is not None:
+        d.pre_hm = pre_hm.data_ptr()
+        d.H, d.W = pre_hm.shape[2:]
+    _lib.check(_lib.load().ct_build_targets(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_targets')

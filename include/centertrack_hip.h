@@ -831,6 +831,43 @@ int ct_preprocess_lut(const float *mean, const float *stdv, int channels, float 
 int ct_preprocess_device(const uint8_t *img, int h, int w, int stride, int channels, const double *trans,
                          int dst_w, int dst_h, const float *lut, float *out, float *out_flip, void *stream);
 
+/* ---- training targets on the device -------------------------------------------------
+ * Replaces, for a whole batch, the dense part of the reference's GenericDataset.__getitem__
+ * (src/lib/dataset/generic_dataset.py:205-255 _get_pre_dets, :330-370 _init_ret, :386-398 _mask_ignore_or_crowd,
+ * :423-515 _add_instance; draw_umich_gaussian, src/lib/utils/image.py:139-154) plus default_collate and
+ * batch[k].to(device): heat maps hm [B,C,h,w] and pre_hm [B,1,H,W] and every slot tensor [B,max_objs,...] are
+ * written by ONE launch from the packed records of the batch, uploaded by ONE asynchronous copy
+ * (staging_host -> staging_dev, `words` int32 words, enqueued by the call itself).
+ * The staging buffer, int32 words (centertrack_amd/targets.py packs it):
+ *   [8 b ..]      per image: slot_off, n_slots, blob_off, n_blobs, rect_off, n_rects, pre_off, n_pre
+ *                 (offsets in words from the start of the buffer, all at or behind the header)
+ *   [8 B ..]      slot map [B][max_objs]: row of the image's slot list that fills slot k, or -1 = hole (zeros)
+ *   [.. ]         column map [slot_words]: index of the output a column of a slot row belongs to
+ *   [.. ]         output table [nout][4]: destination pointer (low, high word; 0 = not asked for),
+ *                 first column | width << 16, 1 = int64 destination (sign-extended) / 0 = 32-bit copy
+ *   slot rows     [n_slots][slot_words] words (float32 bit patterns and int32 values)
+ *   hm blobs      [n_blobs][4]  plane, cx, cy, radius         (Gaussian peak 1)
+ *   rectangles    [n_rects][5]  plane or -1 = all planes, x0, y0, x1, y1 (inclusive): pixels set to 1
+ *   pre_hm blobs  [n_pre][4]    cx, cy, radius, conf          (Gaussian peak conf)
+ * A pixel is max over its Gaussians of float32(exp(-(dx^2+dy^2) / (2 ((2r+1)/6)^2)) * conf) evaluated in float64,
+ * |dx|, |dy| <= r, and 1 inside a rectangle.  hm / pre_hm may be NULL (not written).  Everything is validated on the
+ * host copy before the upload: CT_ERR_ARG for null pointers, non-positive sizes, a plane outside [0, C), counts or
+ * offsets beyond the buffer, a radius outside [0, 16384].  Every output element is written exactly once: the
+ * outputs need no initialisation and two calls agree bit for bit. */
+#define CT_TARGETS_CULL_CAP 256     /* blobs / rectangles a workgroup culls into LDS per round */
+#define CT_TARGETS_MAX_OUT 32
+typedef struct ct_targets_desc {
+    const int *staging_host;        /* pinned HOST copy of the buffer (read by the validation and by the copy) */
+    int *staging_dev;               /* DEVICE buffer of the same size */
+    size_t words;
+    int B, C, h, w;                 /* hm [B,C,h,w] */
+    int H, W;                       /* pre_hm [B,1,H,W] */
+    int max_objs, slot_words, nout;
+    float *hm, *pre_hm;
+} ct_targets_desc;
+size_t ct_build_targets_header_words(int B, int max_objs, int slot_words, int nout);   /* 0 on bad sizes */
+int ct_build_targets(const ct_targets_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
