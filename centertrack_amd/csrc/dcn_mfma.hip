@@ -934,7 +934,20 @@ int make_plan(const ct_dcn_desc *d, DcnPlan *p, bool grouped)
     if (!d->fuse_offset && d->ldom < 27) CT_FAIL_ARG("ct_dcn_v2: offset/mask map needs >= 27 channels");
     if (d->Cout <= 0 || d->N <= 0 || d->H <= 0 || d->W <= 0) CT_FAIL_ARG("ct_dcn_v2: bad shape");
     if (d->flags & CT_OUT_NCHW) CT_FAIL_ARG("ct_dcn_v2: NCHW output unsupported");
+    // What the kernels can address (tests/test_dcn_forward_cpu.py pins each limit from both sides).  The input goes behind one
+    // buffer descriptor per image, here and in the offset/mask conv stages: below 2 GiB per image.  dcn_tab_entry and the direct
+    // store form (pixel index) x (pitch) with 24-bit multiplies: H*W <= 2^23 pixels, ldx * 4 and ldy below 2^23.
+    {
+        const int rc = ct_check_image_view("ct_dcn_v2", "x", d->H, d->W, d->ldx, d->Cin);
+        if (rc != CT_OK) return rc;
+    }
+    if ((double)d->H * d->W > 8388608.0 || d->ldx >= (1 << 21))
+        CT_FAIL_ARG("ct_dcn_v2: %dx%d pixels at input pitch %d: the kernels multiply pixel index and pitch in 24 bits (H*W <= 2^23, ldx < 2^21)",
+                    d->H, d->W, d->ldx);
     p->NT = ct_cdiv(d->Cout, 16);
+    // (the packed weight lies behind one descriptor sized 9 * Cin / 16 * NT KiB as an int, addressed with int byte offsets)
+    if (9.0 * (d->Cin / 16) * p->NT * 1024.0 >= VIEW_LIMIT)
+        CT_FAIL_ARG("ct_dcn_v2: a packed weight of 2 GiB or more (Cin=%d, Cout=%d)", d->Cin, d->Cout);
     p->tilesX = ct_cdiv(d->W, 16);
     p->BM = 64;
     p->BN = 64;
@@ -994,6 +1007,15 @@ int make_plan(const ct_dcn_desc *d, DcnPlan *p, bool grouped)
     p->chunksPerSplit = ct_cdiv(nunits, splits) * upc;
     p->splits = ct_cdiv(p->nchunks, p->chunksPerSplit);
     p->use_ws = (p->splits > 1 || (grouped && d->up_w)) ? 1 : 0;
+    if ((double)tiles * p->splits >= 1073741824.0) CT_FAIL_ARG("ct_dcn_v2: grid too large");
+    if (!p->use_ws) {
+        // the direct store (dcn_store_acc): one descriptor per image whose dropped lanes get the byte offset 0x80000000, and a
+        // 24-bit multiply by the pitch (the finishing launch of a split layer addresses y with 64-bit offsets)
+        const int rc = ct_check_image_view("ct_dcn_v2", "y", d->H, d->W, d->ldy, d->Cout);
+        if (rc != CT_OK) return rc;
+        if (d->ldy >= (1 << 23))
+            CT_FAIL_ARG("ct_dcn_v2: output pitch %d: the kernels multiply pixel index and pitch in 24 bits (ldy < 2^23)", d->ldy);
+    }
     if (p->persist) {
         // every split owns the same EVEN number of step units (the stream of steps keeps its LDS / register parity across
         // tiles), and one buffer descriptor spans the batch
@@ -1001,6 +1023,11 @@ int make_plan(const ct_dcn_desc *d, DcnPlan *p, bool grouped)
         if (p->BM != 32 || (ups & 1) || nunits % ups)
             CT_FAIL_ARG("ct_dcn_v2: persistent shape needs an even number of %d-channel units per split (Cin=%d, split_k=%d)", 16 * p->NKK, d->Cin, p->splits);
         if ((double)d->N * d->H * d->W * d->ldx * 4.0 >= 4294967296.0) CT_FAIL_ARG("ct_dcn_v2: persistent shape: input view of 4 GiB or more");
+        // (the offset / mask map of the whole batch comes through one descriptor too, and lanes outside the map get the byte offset
+        //  0x80000000; partial maps are at most half the size of x: below 2 GiB by the line above)
+        const double px = (double)d->N * d->H * d->W;
+        if (!p->parts && ((px - 1.0) * d->ldom + 27.0) * 4.0 >= VIEW_LIMIT)
+            CT_FAIL_ARG("ct_dcn_v2: persistent shape: offset/mask map of 2 GiB or more (N*H*W=%.0f pixels at pitch %d)", px, d->ldom);
     }
     return CT_OK;
 }
@@ -1054,7 +1081,7 @@ __global__ __launch_bounds__(256) void dcn_reduce_kernel(RedGroup g)
     const unsigned inrow = (unsigned)(bid - row * r.rowBlocks) * 256u + threadIdx.x;
     const float *ws = r.ws;
     const int splits = r.splits, wsCout = r.wsCout;
-    const unsigned plane = (unsigned)r.Mtot * wsCout;     // floats of one split's partial map (< 2^30: host)
+    const unsigned plane = (unsigned)r.Mtot * wsCout;     // floats of one split's partial map (< 2^29: host)
     if (r.u.f == 0) {
         const unsigned quads = wsCout >> 2;
         const unsigned x = inrow / quads;
@@ -1199,10 +1226,12 @@ int launch_group(const ct_dcn_desc *descs, int n, bool grouped, int phases, void
                 r.rowBlocks = (d->W * (r.wsCout / 4) + 255) / 256;
                 rows = (long)d->N * d->H;
             }
-            // (32-bit indices in the kernel: one split's partial map, the output and the skip view in elements)
-            if ((double)r.Mtot * r.wsCout >= 1073741824.0 ||
-                (d->up_w && (double)r.Mtot * d->up_f * d->up_f * (d->up_lds > d->up_ldy ? d->up_lds : d->up_ldy) >= 4294967296.0))
-                CT_FAIL_ARG("ct_dcn_v2: layer %d: partial map / IDAUp output too large for the finishing launch", i);
+            // (one split's partial map lies behind one buffer descriptor of dcn_store_acc whose dropped lanes get the byte offset
+            //  0x80000000: below 2 GiB = 2^29 floats; 32-bit indices in the finishing kernel: the output and the skip view in elements)
+            if ((double)r.Mtot * r.wsCout >= 536870912.0)
+                CT_FAIL_ARG("ct_dcn_v2: layer %d: a partial map of 2 GiB or more (%zu pixels x %d couts) for the finishing launch", i, r.Mtot, r.wsCout);
+            if (d->up_w && (double)r.Mtot * d->up_f * d->up_f * (d->up_lds > d->up_ldy ? d->up_lds : d->up_ldy) >= 4294967296.0)
+                CT_FAIL_ARG("ct_dcn_v2: layer %d: IDAUp output too large for the finishing launch (2^32 elements or more)", i);
             rg.first[rg.n] = (int)rblocks;
             rblocks += rows * r.rowBlocks;
             if (rblocks > 0x7fffffffL) CT_FAIL_ARG("ct_dcn_v2: grid too large");

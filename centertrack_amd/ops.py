@@ -153,8 +153,10 @@ def make_dcn_desc(x, om, wp, Cout, scale, shift, relu, out, workspace=None, spli
     d.x, d.N, d.H, d.W, d.Cin, d.ldx = x.ptr, x.N, x.H, x.W, x.C, x.ld
     if om is not None:
         d.om, d.ldom = om.ptr, om.ld
-    if w_off is not None:
-        d.fuse_offset, d.w_off_packed, d.b_off = 1, w_off.data_ptr(), b_off.data_ptr()
+    if w_off is not None or raw_offsets:             # (raw sums from another launch need b_off only)
+        d.fuse_offset, d.b_off = 1, b_off.data_ptr()
+        if w_off is not None:
+            d.w_off_packed = w_off.data_ptr()
         if om_partial is not None:
             d.fuse_offset = 3 if raw_offsets else 2          # (3: another launch writes the raw sums into om_partial)
             d.om_partial, d.om_partial_bytes = om_partial.data_ptr(), om_partial.numel() * om_partial.element_size()

@@ -11,10 +11,9 @@ import torch
 import torch.nn.functional as F
 
 import _conv_fwd as C
+from _guards import GUARD, NAN, guarded as _guarded, slice_of as _slice_of, take as _take      # (shared with the DCN forward tests)
 
 pytestmark = pytest.mark.gpu
-
-NAN, GUARD = float('nan'), 7.0
 
 
 @contextlib.contextmanager
@@ -28,32 +27,6 @@ def tuning(knobs):
     finally:
         for k, _ in knobs:
             _lib.check(lib.ct_set_tuning(k.encode(), C.KNOBS[k]), k)
-
-
-def _slice_of(t_nchw, device, c0=4, tail=4):
-    """``t`` as the channel slice [c0, c0 + C) of a wider NHWC buffer whose other channels are NaN"""
-    from centertrack_amd import ops
-    N, Cc, H, W = t_nchw.shape
-    buf = torch.full((N, H, W, c0 + (Cc + 3) // 4 * 4 + tail), NAN)
-    buf[..., c0:c0 + Cc] = t_nchw.permute(0, 2, 3, 1)
-    return ops.View(buf.to(device), c0, Cc)
-
-
-def _guarded(N, H, W, Cc, device, c0=4, tail=4):
-    """a NaN-filled output slice between guard channels of 7.0"""
-    from centertrack_amd import ops
-    buf = torch.full((N, H, W, c0 + (Cc + 3) // 4 * 4 + tail), GUARD)
-    buf[..., c0:c0 + Cc] = NAN
-    return ops.View(buf.to(device), c0, Cc)
-
-
-def _take(v, what):
-    """the slice as NCHW on the CPU, after checking that the guards still hold 7.0 and no NaN is left inside"""
-    buf = v.buf.cpu()
-    assert bool((buf[..., :v.c0] == GUARD).all()) and bool((buf[..., v.c0 + v.C:] == GUARD).all()), '%s: wrote outside its slice' % what
-    y = buf[..., v.c0:v.c0 + v.C].permute(0, 3, 1, 2).contiguous()
-    assert not bool(torch.isnan(y).any()), '%s: %d elements never written (or NaN read)' % (what, int(torch.isnan(y).sum()))
-    return y
 
 
 def _guarded_nchw(shape, device, margin=64):
