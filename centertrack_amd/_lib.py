@@ -296,6 +296,19 @@ class TargetsDesc(ctypes.Structure):
                 ('hm', ctypes.c_void_p), ('pre_hm', ctypes.c_void_p)]
 
 
+CT_INPUTS_DESC_WORDS = 48
+CT_INPUTS_TILE_W, CT_INPUTS_TILE_H = 64, 16
+CT_INPUTS_STAGED, CT_INPUTS_DEVICE, CT_INPUTS_ZERO = range(3)
+
+
+class InputsDesc(ctypes.Structure):
+    _fields_ = [('staging_host', ctypes.c_void_p), ('staging_dev', ctypes.c_void_p), ('bytes', ctypes.c_size_t),
+                ('B', ctypes.c_int), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('mean', ctypes.c_float * 3), ('stdv', ctypes.c_float * 3),
+                ('image', ctypes.c_void_p), ('pre_img', ctypes.c_void_p), ('warped', ctypes.c_void_p),
+                ('partials', ctypes.c_void_p), ('gs_mean', ctypes.c_void_p)]
+
+
 ABI_VERSION = 103       # CT_ABI_VERSION of include/centertrack_hip.h
 
 EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_elems', 'ct_pack_conv_weight',
@@ -320,7 +333,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_create', 'ct_frame_loop_destroy', 'ct_frame_loop_submit', 'ct_frame_loop_wait', 'ct_frame_loop_finish',
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
-           'ct_build_targets', 'ct_build_targets_header_words']
+           'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_inputs', 'ct_build_inputs_partials']
 
 _lib = None
 
@@ -473,6 +486,9 @@ def load():
     lib.ct_build_targets_header_words.restype = sz
     lib.ct_build_targets_header_words.argtypes = [i, i, i, i]
     lib.ct_build_targets.argtypes = [ctypes.POINTER(TargetsDesc), p]
+    lib.ct_build_inputs_partials.restype = sz
+    lib.ct_build_inputs_partials.argtypes = [i, i]
+    lib.ct_build_inputs.argtypes = [ctypes.POINTER(InputsDesc), p]
     # CENTERTRACK_TUNE="key=value,key=value": launch-heuristic knobs of ct_set_tuning (A/B runs)
     for kv in filter(None, os.environ.get('CENTERTRACK_TUNE', '').split(',')):
         k, _, v = kv.partition('=')

@@ -8,7 +8,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libcentertrack_hip.so')
-SOURCES = ['api.cpp', 'runtime.hip', 'conv_mfma.hip', 'wino_mfma.hip', 'dcn_mfma.hip', 'dcn_bwd.hip', 'heads_bwd.hip', 'bn_train.hip', 'neck_bwd.hip', 'backbone_bwd.hip', 'loss.hip', 'stem.hip', 'stem_train.hip', 'elementwise.hip', 'decode.hip', 'pose.hip', 'host_track.cpp', 'host_preprocess.cpp', 'preprocess.hip', 'flip.hip', 'frame_loop.hip', 'targets.hip']
+SOURCES = ['api.cpp', 'runtime.hip', 'conv_mfma.hip', 'wino_mfma.hip', 'dcn_mfma.hip', 'dcn_bwd.hip', 'heads_bwd.hip', 'bn_train.hip', 'neck_bwd.hip', 'backbone_bwd.hip', 'loss.hip', 'stem.hip', 'stem_train.hip', 'elementwise.hip', 'decode.hip', 'pose.hip', 'host_track.cpp', 'host_preprocess.cpp', 'preprocess.hip', 'flip.hip', 'frame_loop.hip', 'targets.hip', 'inputs.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC,
          '-Wno-unused-result']
 
@@ -25,7 +25,7 @@ def build(force=False, verbose=False):
     objdir = os.path.join(PKG, 'build')
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, 'ct_common.h'), os.path.join(CSRC, 'ksplit_core.h'), os.path.join(CSRC, 'ct_train.h'),
-               os.path.join(ROOT, 'include', 'centertrack_hip.h')]
+               os.path.join(CSRC, 'ct_warp.h'), os.path.join(ROOT, 'include', 'centertrack_hip.h')]
     objs = []
     procs = []
     for src in SOURCES:

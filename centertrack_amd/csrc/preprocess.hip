@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "ct_common.h"
+#include "ct_warp.h"
 
 namespace {
 
@@ -29,22 +30,11 @@ struct PreArgs {
 
 __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a)
 {
-#pragma clang fp contract(off)
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.dw || y >= a.dh) return;
-    const double AB = 1024.0;
-    const int adelta = __double2int_rn(a.M[0] * (double)x * AB);
-    const int bdelta = __double2int_rn(a.M[3] * (double)x * AB);
-    const int X0 = __double2int_rn((a.M[1] * (double)y + a.M[2]) * AB) + 16;
-    const int Y0 = __double2int_rn((a.M[4] * (double)y + a.M[5]) * AB) + 16;
-    const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    int sx = X >> 5, sy = Y >> 5;
-    sx = max(-32768, min(32767, sx));
-    sy = max(-32768, min(32767, sy));
-    const int fx = X & 31, fy = Y & 31;
-    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32;
-    const int w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+    const CtWarpTaps t = ct_warp_taps(a.M, x, y);       // (csrc/ct_warp.h, shared with inputs.hip)
+    const int sx = t.sx, sy = t.sy;
     const bool x0 = sx >= 0 && sx < a.w, x1 = sx + 1 >= 0 && sx + 1 < a.w;
     const bool y0 = sy >= 0 && sy < a.h, y1 = sy + 1 >= 0 && sy + 1 < a.h;
     const uint8_t *r0 = a.img + (size_t)(y0 ? sy : 0) * a.stride;
@@ -57,8 +47,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a)
         const int p01 = (x1 && y0) ? r0[c1 + c] : 0;
         const int p10 = (x0 && y1) ? r1[c0 + c] : 0;
         const int p11 = (x1 && y1) ? r1[c1 + c] : 0;
-        int v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + (1 << 14)) >> 15;
-        v = max(0, min(255, v));
+        const int v = ct_warp_blend(t, p00, p01, p10, p11);
         const float f = a.lut[c * 256 + v];
         a.out[c * plane + o] = f;
         if (a.out_flip) a.out_flip[c * plane + of] = f;

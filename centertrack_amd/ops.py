@@ -983,3 +983,22 @@ def build_targets(staging_host, staging_dev, words, B, max_objs, slot_words, nou
         d.pre_hm = pre_hm.data_ptr()
         d.H, d.W = pre_hm.shape[2:]
     _lib.check(_lib.load().ct_build_targets(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_targets')
+
+
+def build_inputs(staging_host, staging_dev, nbytes, B, N, H, W, mean, std, image, pre_img, warped, partials,
+                 gs_mean=None):
+    """ct_build_inputs (csrc/inputs.hip) on the current stream: upload ``nbytes`` bytes of descriptors and u8 source rows
+    from the pinned ``staging_host`` to ``staging_dev`` and write image [B,3,H,W] (and pre_img, with N = 2 B) in two
+    launches.  ``warped`` int32 [N,H,W] and ``partials`` float64 [N * ct_build_inputs_partials(H, W)] are scratch,
+    ``gs_mean`` float32 [N] is optional.  ``centertrack_amd.inputs.InputBuilder.render`` packs the buffer; bad contents
+    raise ``CTError`` before anything is enqueued."""
+    d = _lib.InputsDesc()
+    d.staging_host, d.staging_dev, d.bytes = staging_host.data_ptr(), staging_dev.data_ptr(), nbytes
+    d.B, d.N, d.H, d.W = B, N, H, W
+    for c in range(3):
+        d.mean[c], d.stdv[c] = float(mean[c]), float(std[c])
+    d.image = image.data_ptr()
+    d.pre_img = pre_img.data_ptr() if pre_img is not None else None
+    d.warped, d.partials = warped.data_ptr(), partials.data_ptr()
+    d.gs_mean = gs_mean.data_ptr() if gs_mean is not None else None
+    _lib.check(_lib.load().ct_build_inputs(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_inputs')

@@ -25,8 +25,8 @@ A record holds
   ``rects``      int32 [nr, 5]  plane or -1 (all planes), x0, y0, x1, y1 (inclusive): ignore / crowd regions
   ``pre_blobs``  int32 [np, 4]  cx, cy, radius, conf
 
-The loaders, the augmentation parameters, the flip of the annotations and the image warp stay the caller's; the pose
-heads (``hps``, ``hm_hp``, ``hp_offset``) and ``opt.dense_reg != 1`` are refused.
+The loaders, the augmentation parameters and the flip of the annotations stay the caller's (the images of the batch:
+``inputs.InputBuilder``); the pose heads (``hps``, ``hm_hp``, ``hp_offset``) and ``opt.dense_reg != 1`` are refused.
 """
 import math
 
@@ -333,16 +333,8 @@ class TargetBuilder(object):
         """a pinned int32 block no call in flight still reads: an idle ring entry that is large enough, else a new one
         (never a wait: ``event.query()`` only asks)"""
         import torch
-        for e in self._ring:
-            if e['host'].numel() >= words and e['event'].query():
-                return e
-        self._ring = [e for e in self._ring if not (e['host'].numel() < words and e['event'].query())]
-        cap = 4096
-        while cap < words:
-            cap *= 2
-        e = {'host': torch.empty(cap, dtype=torch.int32).pin_memory(), 'event': torch.cuda.Event()}
-        self._ring.append(e)
-        return e
+        from . import _staging
+        return _staging.take(self._ring, words, torch.int32)
 
     def render(self, records, device=None, out=None):
         """The batch ``default_collate`` + ``.to(device)`` would have made of the reference's samples (images excluded):

@@ -868,6 +868,54 @@ typedef struct ct_targets_desc {
 size_t ct_build_targets_header_words(int B, int max_objs, int slot_words, int nout);   /* 0 on bad sizes */
 int ct_build_targets(const ct_targets_desc *d, void *stream);
 
+/* ---- training images on the device (additions under ABI 103) ---------------------------
+ * Replaces, for a whole batch, GenericDataset._get_input (src/lib/dataset/generic_dataset.py:317-327:
+ * cv2.warpAffine, astype(float32) / 255., color_aug of src/lib/utils/image.py:211-243, (x - mean) / std,
+ * HWC -> CHW), the flip of the frame (:90,107), default_collate and .to(device), for `image` and `pre_img`
+ * together: N = B or 2 B images of H x W in TWO launches behind ONE asynchronous copy (staging_host ->
+ * staging_dev, `bytes` bytes, enqueued by the call itself).
+ * The staging buffer (centertrack_amd/inputs.py packs it): N descriptors of CT_INPUTS_DESC_WORDS int32 words,
+ * image n = slot * B + b (slot 0: image, slot 1: pre_img), then the u8 source rows of the images that are not
+ * on the device yet.  Words of a descriptor:
+ *   0        kind: CT_INPUTS_STAGED (rows in this buffer), CT_INPUTS_DEVICE (rows on the device) or
+ *            CT_INPUTS_ZERO (no source: the output image is 0.0f everywhere, nothing else is read)
+ *   1        byte offset of the rows from the start of the buffer (staged), at or behind the descriptors
+ *   2, 3     device address of the rows (device), low and high word
+ *   4 .. 8   h, w of the WHOLE source image, row pitch in bytes (>= 3 w), row0, nrows: the rows
+ *            [row0, row0 + nrows) of the image are present; taps on other rows, like taps outside the image, are 0
+ *   9        flipped (0 / 1): the source column is mirrored, w - 1 - sx, as if img[:, ::-1] were warped
+ *   10       colour augmentation on (0 / 1)
+ *   11 .. 13 the order of the three functions: 0 brightness, 1 contrast, 2 saturation (a permutation)
+ *   14 .. 16 float32 alpha of each function in call order;  17 .. 19 float32(1 - alpha), formed in double
+ *   20 .. 25 the lighting vector, 3 float64 (B, G, R)
+ *   28 .. 39 trans_input, 6 float64 (the forward 2 x 3 map; the call inverts it like cv::warpAffine and writes
+ *            the inverse over it in staging_host before the copy)
+ * Pass 1 warps with OpenCV's fixed-point arithmetic (bit-identical to ct_preprocess_image) into `warped`
+ * [N][H][W] (B, G, R in the low three bytes of a word) and stores one float64 partial sum of the float32 grey
+ * value per CT_INPUTS_TILE_W x CT_INPUTS_TILE_H tile into `partials` [N][ct_build_inputs_partials(H, W)];
+ * pass 2 adds an image's partials in index order, forms gs_mean and writes float32 NCHW planes: every element
+ * of image [B,3,H,W] (and pre_img, if given) exactly once.  No memset, no atomics, no host wait; the arguments
+ * are checked on staging_host before anything is enqueued. */
+#define CT_INPUTS_DESC_WORDS 48
+#define CT_INPUTS_TILE_W 64
+#define CT_INPUTS_TILE_H 16
+#define CT_INPUTS_STAGED 0
+#define CT_INPUTS_DEVICE 1
+#define CT_INPUTS_ZERO 2
+typedef struct ct_inputs_desc {
+    int *staging_host;              /* pinned HOST copy of the buffer */
+    int *staging_dev;               /* DEVICE buffer of the same size */
+    size_t bytes;
+    int B, N, H, W;                 /* N = B (image only) or 2 B (image and pre_img) */
+    float mean[3], stdv[3];         /* the dataset's mean / std (B, G, R) */
+    float *image, *pre_img;         /* DEVICE fp32 [B,3,H,W]; pre_img NULL when N = B */
+    unsigned *warped;               /* DEVICE scratch [N][H][W] */
+    double *partials;               /* DEVICE scratch [N][ct_build_inputs_partials(H, W)] */
+    float *gs_mean;                 /* optional DEVICE [N]: the mean grey value of each warped image */
+} ct_inputs_desc;
+size_t ct_build_inputs_partials(int H, int W);          /* partial sums per image; 0 on bad sizes */
+int ct_build_inputs(const ct_inputs_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
