@@ -296,6 +296,10 @@ class TargetsDesc(ctypes.Structure):
                 ('hm', ctypes.c_void_p), ('pre_hm', ctypes.c_void_p)]
 
 
+class PoseTargetsDesc(ctypes.Structure):
+    _fields_ = [('base', TargetsDesc), ('hm_hp', ctypes.c_void_p), ('J', ctypes.c_int)]
+
+
 CT_INPUTS_DESC_WORDS = 48
 CT_INPUTS_TILE_W, CT_INPUTS_TILE_H = 64, 16
 CT_INPUTS_STAGED, CT_INPUTS_DEVICE, CT_INPUTS_ZERO = range(3)
@@ -333,7 +337,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_create', 'ct_frame_loop_destroy', 'ct_frame_loop_submit', 'ct_frame_loop_wait', 'ct_frame_loop_finish',
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
-           'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_inputs', 'ct_build_inputs_partials']
+           'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials']
 
 _lib = None
 
@@ -486,6 +490,7 @@ def load():
     lib.ct_build_targets_header_words.restype = sz
     lib.ct_build_targets_header_words.argtypes = [i, i, i, i]
     lib.ct_build_targets.argtypes = [ctypes.POINTER(TargetsDesc), p]
+    lib.ct_build_pose_targets.argtypes = [ctypes.POINTER(PoseTargetsDesc), p]
     lib.ct_build_inputs_partials.restype = sz
     lib.ct_build_inputs_partials.argtypes = [i, i]
     lib.ct_build_inputs.argtypes = [ctypes.POINTER(InputsDesc), p]

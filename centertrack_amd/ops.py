@@ -985,6 +985,27 @@ def build_targets(staging_host, staging_dev, words, B, max_objs, slot_words, nou
     _lib.check(_lib.load().ct_build_targets(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_targets')
 
 
+def build_pose_targets(staging_host, staging_dev, words, B, max_objs, slot_words, nout, C, J, hw, hm=None, pre_hm=None,
+                       hm_hp=None):
+    """ct_build_pose_targets (csrc/targets.hip) on the current stream: ``build_targets`` plus hm_hp [B,J,h,w] in the same
+    launch.  ``C`` class planes and ``J`` joint planes of ``hw`` = (h, w) number the planes of the lists whichever maps
+    are asked for (each of hm, pre_hm, hm_hp may be None).  ``centertrack_amd.targets.PoseTargetBuilder.render`` packs
+    the buffer; bad contents raise ``CTError`` before anything is enqueued."""
+    d = _lib.PoseTargetsDesc()
+    t = d.base
+    t.staging_host, t.staging_dev, t.words = staging_host.data_ptr(), staging_dev.data_ptr(), words
+    t.B, t.max_objs, t.slot_words, t.nout = B, max_objs, slot_words, nout
+    t.C, (t.h, t.w), d.J = C, hw, J
+    if hm is not None:
+        t.hm = hm.data_ptr()
+    if hm_hp is not None:
+        d.hm_hp = hm_hp.data_ptr()
+    if pre_hm is not None:
+        t.pre_hm = pre_hm.data_ptr()
+        t.H, t.W = pre_hm.shape[2:]
+    _lib.check(_lib.load().ct_build_pose_targets(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_pose_targets')
+
+
 def build_inputs(staging_host, staging_dev, nbytes, B, N, H, W, mean, std, image, pre_img, warped, partials,
                  gs_mean=None):
     """ct_build_inputs (csrc/inputs.hip) on the current stream: upload ``nbytes`` bytes of descriptors and u8 source rows

@@ -25,8 +25,23 @@ A record holds
   ``rects``      int32 [nr, 5]  plane or -1 (all planes), x0, y0, x1, y1 (inclusive): ignore / crowd regions
   ``pre_blobs``  int32 [np, 4]  cx, cy, radius, conf
 
-The loaders, the augmentation parameters and the flip of the annotations stay the caller's (the images of the batch:
-``inputs.InputBuilder``); the pose heads (``hps``, ``hm_hp``, ``hp_offset``) and ``opt.dense_reg != 1`` are refused.
+The loaders, the augmentation parameters and the flip of the annotations (boxes and key points) stay the caller's (the
+images of the batch: ``inputs.InputBuilder``); ``opt.dense_reg != 1`` is refused.
+
+The pose task (``tracking,multi_pose``) is ``PoseTargetBuilder``: ``TargetBuilder`` itself keeps
+refusing the pose heads (``hps``, ``hm_hp``, ``hp_offset``).  It restates ``_add_hps`` (generic_dataset.py:517-554) and
+the ``hm_hp`` line of ``_mask_ignore_or_crowd`` (:396-398) in ``encode``, and its records have the same six arrays:
+
+* the J planes of ``hm_hp`` are numbered ``C .. C+J-1`` behind the class planes: a visible joint inside the map is one
+  more row of ``hm_blobs`` (plane ``C + j``, the truncated point, the object's radius), an unlabelled joint one more row
+  of ``rects`` (plane ``C + j``, the object's clipped box), and an ignore / crowd annotation of class id <= 1 a row
+  with plane -2 = all ``hm_hp`` planes (next to its row for ``hm``: -1 = all class planes, or one of them);
+* ``hps`` / ``hps_mask`` [2J] are head columns of the slot row like ``wh``; the joint tensors -- ``hm_hp_mask`` [J],
+  ``hp_offset`` [J,2], ``hp_ind`` [J] int64, ``hp_offset_mask`` [J,2], ``joint`` [J] int64 per object, which the
+  reference shapes ``[max_objs*J, ..]`` -- are further columns of it: ``[B, max_objs*J, 2]`` is ``[B, max_objs, 2J]``
+  in memory.
+
+``render`` then goes through ``ct_build_pose_targets``: ``hm_hp`` [B,J,h,w] comes out of the same launch.
 """
 import math
 
@@ -44,6 +59,8 @@ MAX_OUT = _lib.CT_TARGETS_MAX_OUT
 # (head, channels) in the order the reference's _init_ret creates them
 HEAD_DIMS = (('reg', 2), ('wh', 2), ('tracking', 2), ('ltrb', 4), ('ltrb_amodal', 4), ('nuscenes_att', 8),
              ('velocity', 3), ('dep', 1), ('dim', 3), ('amodel_offset', 2))
+HPS_AFTER = 'velocity'                       # _init_ret creates hps / hps_mask [2J] behind this head
+ALL_HM, ALL_HM_HP = -1, -2                   # rectangle plane codes: every class plane / every hm_hp plane
 POSE_HEADS = ('hps', 'hm_hp', 'hp_offset')
 NO_NOISE = (0.0, 0.0, 1.0, 1.0, 0.0, 0.0)    # no shift, kept (uniform 1 > lost_disturb), no false positive
 
@@ -75,11 +92,14 @@ class _Draws(object):
 
 
 class TargetBuilder(object):
+    num_joints = 0                               # PoseTargetBuilder: J
+
     def __init__(self, opt, num_classes, max_objs, cat_ids, nuscenes_att_range=None):
         heads = list(opt.heads)
         bad = [h for h in POSE_HEADS if h in heads]
-        if bad:
-            raise CTError('TargetBuilder: the pose heads are not covered (%s)' % ', '.join(bad))
+        if bad and not self.num_joints:
+            raise CTError('TargetBuilder: the pose heads are not covered (%s); PoseTargetBuilder builds them'
+                          % ', '.join(bad))
         if getattr(opt, 'dense_reg', 1) != 1:
             raise CTError('TargetBuilder: opt.dense_reg = %r is not supported (1 only)' % (opt.dense_reg,))
         if num_classes < 1 or max_objs < 1:
@@ -92,9 +112,10 @@ class TargetBuilder(object):
         self.pre_hm = self.tracking and bool(getattr(opt, 'pre_hm', False))
         # (name, width, int64?, shape behind [B, max_objs]) of every slot tensor, in record-column order
         outs = [('ind', 1, True, ()), ('cat', 1, True, ()), ('mask', 1, False, ())]
-        for h, d in HEAD_DIMS:
+        for h, d in self._head_dims():
             if h in heads:
                 outs += [(h, d, False, (d,)), (h + '_mask', d, False, (d,))]
+        outs += self._joint_outputs()
         if 'rot' in heads:
             outs += [('rotbin', 2, True, (2,)), ('rotres', 2, False, (2,)), ('rot_mask', 1, False, ())]
         self.outputs = outs
@@ -104,6 +125,16 @@ class TargetBuilder(object):
             c += wd
         self.slot_words = c
         self._ring = []
+
+    def _head_dims(self):
+        return HEAD_DIMS
+
+    def _joint_outputs(self):
+        return []
+
+    def _tail(self, name, tail):
+        """the shape of a slot tensor behind the batch axis"""
+        return (self.max_objs,) + tail
 
     # ------------------------------------------------------------------ host: encode
     @staticmethod
@@ -230,6 +261,9 @@ class TargetBuilder(object):
             slot['amodel_offset'][:] = centre - ct_int
         return (cls_id - 1, int(ct_int[0]), int(ct_int[1]), radius)
 
+    def _joints(self, slot, ann, trans_output, blob, bbox, blobs, rects):
+        """the key points of one object (PoseTargetBuilder)"""
+
     def encode(self, anns, trans_output, height, width, aug_s=1, calib=None, pre_anns=None, trans_input_pre=None,
                trans_output_pre=None, noise=None, rng=None):
         """The record of one sample.  ``anns`` / ``pre_anns``: the annotation lists as the reference's object loop sees
@@ -262,14 +296,17 @@ class TargetBuilder(object):
                 if plane >= self.num_classes:
                     raise CTError('TargetBuilder.encode: ignore class %d has no heat-map plane' % cls_id)
                 rects.append((plane, int(bbox[0]), int(bbox[1]), int(bbox[2]), int(bbox[3])))
+                if self.num_joints and cls_id <= 1:
+                    rects.append((ALL_HM_HP,) + rects[-1][1:])
                 continue
             slot = self._new_slot()
             blob = self._instance(slot, cls_id, bbox, amodal, ann, trans_output, aug_s, pre_cts, track_ids)
             if blob is None:
                 continue
+            blobs.append(blob)
+            self._joints(slot, ann, trans_output, blob, bbox, blobs, rects)
             slot_k.append(k)
             slot_v.append(self._pack_slot(slot))
-            blobs.append(blob)
         rec = {'slot_k': np.array(slot_k, np.int32).reshape(-1),
                'slot_v': np.array(slot_v, np.int32).reshape(-1, self.slot_words),
                'hm_blobs': np.array(blobs, np.int32).reshape(-1, 4),
@@ -302,19 +339,24 @@ class TargetBuilder(object):
             for cx, cy, r, conf in rec['pre_blobs'].tolist():
                 draw_umich_gaussian(pre[0], (cx, cy), r, k=conf)
             ret['pre_hm'] = pre
-        hm = np.zeros((self.num_classes, opt.output_h, opt.output_w), np.float32)
+        C, J = self.num_classes, self.num_joints
+        maps = np.zeros((C + J, opt.output_h, opt.output_w), np.float32)       # hm, then hm_hp: the record's planes
         for name, wd, i64, tail in self.outputs:
-            ret[name] = np.zeros((self.max_objs,) + tail, np.int64 if i64 else np.float32)
+            full = np.zeros((self.max_objs, wd), np.int64 if i64 else np.float32)
             c = self.columns[name]
             for row, k in enumerate(rec['slot_k'].tolist()):
                 v = np.ascontiguousarray(rec['slot_v'][row, c:c + wd])
-                ret[name][k] = (v.astype(np.int64) if i64 else v.view(np.float32)).reshape(tail)
+                full[k] = v.astype(np.int64) if i64 else v.view(np.float32)
+            ret[name] = full.reshape(self._tail(name, tail))
         for plane, x0, y0, x1, y1 in rec['rects'].tolist():
-            region = hm[:, y0:y1 + 1, x0:x1 + 1] if plane < 0 else hm[plane, y0:y1 + 1, x0:x1 + 1]
+            which = plane if plane >= 0 else slice(C, C + J) if J and plane == ALL_HM_HP else slice(0, C)
+            region = maps[which, y0:y1 + 1, x0:x1 + 1]
             np.maximum(region, 1, out=region)
         for plane, cx, cy, r in rec['hm_blobs'].tolist():
-            draw_umich_gaussian(hm[plane], (cx, cy), r)
-        ret['hm'] = hm
+            draw_umich_gaussian(maps[plane], (cx, cy), r)
+        ret['hm'] = maps[:C]
+        if J:
+            ret['hm_hp'] = maps[C:]
         return ret
 
     # ------------------------------------------------------------------ device: render
@@ -325,8 +367,10 @@ class TargetBuilder(object):
         specs = {'hm': ((B, self.num_classes, opt.output_h, opt.output_w), torch.float32)}
         if self.pre_hm:
             specs['pre_hm'] = ((B, 1, opt.input_h, opt.input_w), torch.float32)
+        if self.num_joints:
+            specs['hm_hp'] = ((B, self.num_joints, opt.output_h, opt.output_w), torch.float32)
         for name, _, i64, tail in self.outputs:
-            specs[name] = ((B, self.max_objs) + tail, torch.int64 if i64 else torch.float32)
+            specs[name] = ((B,) + self._tail(name, tail), torch.int64 if i64 else torch.float32)
         return specs
 
     def _staging(self, words):
@@ -404,6 +448,71 @@ class TargetBuilder(object):
             o += p.size
         with torch.cuda.device(device):
             dev = torch.empty(words, dtype=torch.int32, device=device)
-            ops.build_targets(entry['host'], dev, words, B, M, S, nout, out.get('hm'), out.get('pre_hm'))
+            if self.num_joints:
+                ops.build_pose_targets(entry['host'], dev, words, B, M, S, nout, self.num_classes, self.num_joints,
+                                       (self.opt.output_h, self.opt.output_w), out.get('hm'), out.get('pre_hm'),
+                                       out.get('hm_hp'))
+            else:
+                ops.build_targets(entry['host'], dev, words, B, M, S, nout, out.get('hm'), out.get('pre_hm'))
             entry['event'].record()
         return out
+
+
+class PoseTargetBuilder(TargetBuilder):
+    """``TargetBuilder`` for the pose task: ``hps`` and ``hm_hp`` (both required), ``hp_offset`` optional as a head -- the
+    reference creates its targets with ``hm_hp`` either way (generic_dataset.py:352-363).  The flip of the key points
+    (``_flip_anns`` with the dataset's ``flip_idx``) is the caller's, like the flip of the boxes."""
+
+    def __init__(self, opt, num_classes, max_objs, cat_ids, nuscenes_att_range=None, num_joints=17):
+        heads = list(opt.heads)
+        if ('hps' in heads) != ('hm_hp' in heads) or 'hps' not in heads:
+            # hps alone: _add_hps writes ret['hp_offset'], which only hm_hp creates; hm_hp alone: no configuration
+            raise CTError('PoseTargetBuilder: the heads must hold both hps and hm_hp (%s)' % ', '.join(heads))
+        if getattr(opt, 'simple_radius', 0) > 0:
+            raise CTError('PoseTargetBuilder: opt.simple_radius = %r is not supported (the reference calls a function '
+                          'it does not define)' % (opt.simple_radius,))
+        if int(num_joints) < 1:
+            raise CTError('PoseTargetBuilder: num_joints must be positive')
+        self.num_joints = int(num_joints)
+        super(PoseTargetBuilder, self).__init__(opt, num_classes, max_objs, cat_ids, nuscenes_att_range)
+        if self.slot_words > 0xffff or len(self.outputs) > MAX_OUT:
+            raise CTError('PoseTargetBuilder: %d joints do not fit a slot row' % self.num_joints)
+
+    def _head_dims(self):
+        i = [h for h, _ in HEAD_DIMS].index(HPS_AFTER) + 1
+        return HEAD_DIMS[:i] + (('hps', 2 * self.num_joints),) + HEAD_DIMS[i:]
+
+    def _joint_outputs(self):
+        J = self.num_joints
+        return [('hm_hp_mask', J, False, ()), ('hp_offset', 2 * J, False, (2,)), ('hp_ind', J, True, ()),
+                ('hp_offset_mask', 2 * J, False, (2,)), ('joint', J, True, ())]
+
+    def _tail(self, name, tail):
+        if name in ('hm_hp_mask', 'hp_offset', 'hp_ind', 'hp_offset_mask', 'joint'):
+            return (self.max_objs * self.num_joints,) + tail
+        return (self.max_objs,) + tail
+
+    def _joints(self, slot, ann, trans_output, blob, bbox, blobs, rects):
+        """_add_hps with numpy's dtypes: ``pts`` is float32; the affine map and the two differences are taken in float64
+        and rounded once into their float32 slots; the in-bounds test is on the float32 point; int32 truncates"""
+        opt, J, C = self.opt, self.num_joints, self.num_classes
+        pts = (np.array(ann['keypoints'], np.float32).reshape(J, 3) if 'keypoints' in ann
+               else np.zeros((J, 3), np.float32))
+        ct_int = np.array(blob[1:3], np.int32)
+        radius = blob[3]                         # hp_radius: the object's own radius
+        for j in range(J):
+            pts[j, :2] = affine_transform(pts[j, :2], trans_output)
+            if pts[j, 2] > 0:
+                if 0 <= pts[j, 0] < opt.output_w and 0 <= pts[j, 1] < opt.output_h:
+                    slot['hps'][2 * j:2 * j + 2] = pts[j, :2].astype(np.float64) - ct_int
+                    slot['hps_mask'][2 * j:2 * j + 2] = 1
+                    pt_int = pts[j, :2].astype(np.int32)
+                    slot['hp_offset'][2 * j:2 * j + 2] = pts[j, :2].astype(np.float64) - pt_int
+                    slot['hp_ind'][j] = int(pt_int[1]) * opt.output_w + int(pt_int[0])
+                    seen = 0 if pts[j, 2] == 1 else 1      # visibility 1: drawn, indexed, but not learnt from
+                    slot['hp_offset_mask'][2 * j:2 * j + 2] = seen
+                    slot['hm_hp_mask'][j] = seen
+                    slot['joint'][j] = j
+                    blobs.append((C + j, int(pt_int[0]), int(pt_int[1]), radius))
+            else:
+                rects.append((C + j, int(bbox[0]), int(bbox[1]), int(bbox[2]), int(bbox[3])))

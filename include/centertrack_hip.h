@@ -868,6 +868,24 @@ typedef struct ct_targets_desc {
 size_t ct_build_targets_header_words(int B, int max_objs, int slot_words, int nout);   /* 0 on bad sizes */
 int ct_build_targets(const ct_targets_desc *d, void *stream);
 
+/* ---- pose training targets (an addition under ABI 103) ----------------------------------
+ * ct_build_targets plus the key-point heat map hm_hp [B,J,h,w] of the reference's _add_hps
+ * (src/lib/dataset/generic_dataset.py:517-554) and the hm_hp line of _mask_ignore_or_crowd (:396-398), in the SAME
+ * launch behind the SAME copy.  Same staging buffer; the J hm_hp planes are numbered C .. C+J-1 behind the class
+ * planes: a blob (plane, cx, cy, radius) with plane >= C is a joint's Gaussian, a rectangle's plane may be any of
+ * [0, C+J), -1 = all class planes or -2 = all hm_hp planes.  The joint tensors (hm_hp_mask, hp_offset, hp_ind,
+ * hp_offset_mask, joint: [B, max_objs*J, ..] = [B, max_objs, J ..] in memory) are columns of the slot rows like
+ * any other.  hm_hp may be NULL (not asked for); J says how many planes the lists may name either way, and J = 0
+ * accepts exactly what ct_build_targets accepts.  CT_ERR_ARG, before the upload, for J < 0, hm_hp with J <= 0, a
+ * blob plane outside [0, C+J), a rectangle plane outside [-2, C+J) (J = 0: [-1, C)), and everything
+ * ct_build_targets refuses. */
+typedef struct ct_pose_targets_desc {
+    ct_targets_desc base;           /* every field as for ct_build_targets */
+    float *hm_hp;                   /* DEVICE fp32 [B,J,h,w] or NULL */
+    int J;
+} ct_pose_targets_desc;
+int ct_build_pose_targets(const ct_pose_targets_desc *d, void *stream);
+
 /* ---- training images on the device (additions under ABI 103) ---------------------------
  * Replaces, for a whole batch, GenericDataset._get_input (src/lib/dataset/generic_dataset.py:317-327:
  * cv2.warpAffine, astype(float32) / 255., color_aug of src/lib/utils/image.py:211-243, (x - mean) / std,

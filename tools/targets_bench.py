@@ -10,13 +10,15 @@ Both are timed with wall time around the whole thing (one thread, synchronised a
 what they enqueue (the uploads / the copy and the launch); the host parts are also given one by one.  A DataLoader
 spreads the per-sample host work over its workers; the figures here are per batch on ONE core, so divide the per-sample
 parts by the number of workers to compare.  Configurations: ``mot`` (1 class, 512 x 512, B = 32, about 30 objects,
-tracking with pre_hm and the disturbances of the MOT experiments) and ``coco`` (80 classes, 512 x 512, B = 32, about 20
-objects, no pre_hm).  Annotations are synthetic: nothing outside the repository is read.
+tracking with pre_hm and the disturbances of the MOT experiments), ``coco`` (80 classes, 512 x 512, B = 32, about 20
+objects, no pre_hm) and ``pose`` (1 class, 512 x 512, B = 32, about 8 persons with 17 key points
+each, the heads of ``tracking,multi_pose``, through ``PoseTargetBuilder``).  Annotations are synthetic: nothing outside
+the repository is read.
 
 Appends one line per configuration to profiles/targets_bench.jsonl; the first line of a run carries ``box_calibration``
 (tools/box_calib.py).
 
-    python tools/targets_bench.py [--configs mot,coco] [--steps 10] [--warmup 2] [--rounds 3]
+    python tools/targets_bench.py [--configs mot,coco,pose] [--steps 10] [--warmup 2] [--rounds 3]
 """
 import argparse
 import json
@@ -34,11 +36,13 @@ if ROOT not in sys.path:
 CONFIGS = {'mot': dict(C=1, hw=(512, 512), B=32, objs=30, tracking=True, max_objs=256,
                        heads=('hm', 'reg', 'wh', 'tracking', 'ltrb_amodal'), disturb=(0.05, 0.4, 0.1)),
            'coco': dict(C=80, hw=(512, 512), B=32, objs=20, tracking=False, max_objs=128,
-                        heads=('hm', 'reg', 'wh'), disturb=(0.0, 0.0, 0.0))}
+                        heads=('hm', 'reg', 'wh'), disturb=(0.0, 0.0, 0.0)),
+           'pose': dict(C=1, hw=(512, 512), B=32, objs=8, tracking=True, max_objs=32, joints=17,
+                        heads=('hm', 'reg', 'wh', 'tracking', 'hps', 'hm_hp', 'hp_offset'), disturb=(0.05, 0.4, 0.1))}
 
 
 def make_builder(cfg):
-    from centertrack_amd.targets import TargetBuilder
+    from centertrack_amd.targets import PoseTargetBuilder, TargetBuilder
     o = types.SimpleNamespace()
     o.heads = {h: 1 for h in cfg['heads']}
     o.num_classes = cfg['C']
@@ -48,7 +52,10 @@ def make_builder(cfg):
     o.tracking = o.pre_hm = cfg['tracking']
     o.hm_disturb, o.lost_disturb, o.fp_disturb = cfg['disturb']
     o.dense_reg = 1
-    return TargetBuilder(o, cfg['C'], cfg['max_objs'], {i: i for i in range(1, cfg['C'] + 1)})
+    cat_ids = {i: i for i in range(1, cfg['C'] + 1)}
+    if cfg.get('joints'):
+        return PoseTargetBuilder(o, cfg['C'], cfg['max_objs'], cat_ids, num_joints=cfg['joints'])
+    return TargetBuilder(o, cfg['C'], cfg['max_objs'], cat_ids)
 
 
 def make_samples(cfg, seed):
@@ -61,6 +68,13 @@ def make_samples(cfg, seed):
             w, h = rs.uniform(8, W * 0.3), rs.uniform(8, H * 0.4)
             anns.append({'bbox': [float(rs.uniform(-w / 4, W - w * 0.75)), float(rs.uniform(-h / 4, H - h * 0.75)),
                                   float(w), float(h)], 'category_id': int(rs.randint(1, cfg['C'] + 1)), 'track_id': i})
+            if cfg.get('joints'):              # key points over the box widened by 10 %; visibility 2 / 1 / 0 as 6 : 3 : 1
+                x, y = anns[-1]['bbox'][:2]
+                kp = []
+                for _ in range(cfg['joints']):
+                    kp += [float(rs.uniform(x - 0.1 * w, x + 1.1 * w)), float(rs.uniform(y - 0.1 * h, y + 1.1 * h)),
+                           int(rs.choice([2, 2, 2, 2, 2, 2, 1, 1, 1, 0]))]
+                anns[-1]['keypoints'] = kp
         samples.append(anns)
     return samples
 
