@@ -313,6 +313,19 @@ class InputsDesc(ctypes.Structure):
                 ('partials', ctypes.c_void_p), ('gs_mean', ctypes.c_void_p)]
 
 
+CT_OPTIM_ADAM, CT_OPTIM_SGD = range(2)
+CT_OPTIM_CHUNK = 4096
+CT_OPTIM_REC_BYTES = 128
+CT_OPTIM_SCALARS = 8
+CT_OPTIM_MAX_TENSORS = 1 << 20
+
+
+class OptimRec(ctypes.Structure):
+    _fields_ = [('p', ctypes.c_void_p), ('g', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p),
+                ('numel', ctypes.c_longlong), ('s', ctypes.c_float * CT_OPTIM_SCALARS), ('first', ctypes.c_int),
+                ('reserved', ctypes.c_int * 13)]
+
+
 ABI_VERSION = 103       # CT_ABI_VERSION of include/centertrack_hip.h
 
 EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_elems', 'ct_pack_conv_weight',
@@ -337,7 +350,8 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_create', 'ct_frame_loop_destroy', 'ct_frame_loop_submit', 'ct_frame_loop_wait', 'ct_frame_loop_finish',
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
-           'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials']
+           'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials',
+           'ct_optim_step']
 
 _lib = None
 
@@ -494,6 +508,7 @@ def load():
     lib.ct_build_inputs_partials.restype = sz
     lib.ct_build_inputs_partials.argtypes = [i, i]
     lib.ct_build_inputs.argtypes = [ctypes.POINTER(InputsDesc), p]
+    lib.ct_optim_step.argtypes = [p, i, ctypes.c_longlong, i, p]
     # CENTERTRACK_TUNE="key=value,key=value": launch-heuristic knobs of ct_set_tuning (A/B runs)
     for kv in filter(None, os.environ.get('CENTERTRACK_TUNE', '').split(',')):
         k, _, v = kv.partition('=')

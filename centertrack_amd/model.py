@@ -886,10 +886,11 @@ def create_model(arch, head, head_conv, opt=None):
 
 
 def load_model(model, model_path, opt=None, optimizer=None):
-    """reference model.py:31-90 (inference part): ``{'epoch', 'state_dict'}`` checkpoint, ``module.`` prefix
+    """reference model.py:31-90: ``{'epoch', 'state_dict'[, 'optimizer']}`` checkpoint, ``module.`` prefix
     stripped, unknown keys dropped, missing keys keep their initialisation; a parameter whose shape differs -- or,
     under ``opt.reset_hm``, an ``hm*`` parameter with 80 / 1 rows -- is skipped, or with ``opt.reuse_hm`` cut /
-    padded along its first axis (a COCO-pretrained heat-map head reused for another class count, model.py:49-63)."""
+    padded along its first axis (a COCO-pretrained heat-map head reused for another class count, model.py:49-63).
+    With an ``optimizer`` it returns ``(model, optimizer, start_epoch)`` as the reference does (below)."""
     ckpt = torch.load(model_path, map_location='cpu')
     sd_in = ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
     if 'epoch' in ckpt:
@@ -923,4 +924,34 @@ def load_model(model, model_path, opt=None, optimizer=None):
         if k not in keep:
             print('No param {}.'.format(k))
     model.load_state_dict(keep, strict=False)
-    return model
+    if optimizer is None:
+        return model
+    # the resume branch, model.py:73-90.  Like the reference it does NOT load the optimizer state (that line is commented
+    # out there): it takes the epoch and restarts the learning rate -- opt.lr times 0.1 once per passed lr_step, one
+    # multiplication after the other, which in floating point is not main.py's opt.lr * 0.1 ** k.
+    start_epoch = 0
+    if getattr(opt, 'resume', False):
+        if 'optimizer' in ckpt:
+            start_epoch = ckpt['epoch']
+            start_lr = opt.lr
+            for step in opt.lr_step:
+                if start_epoch >= step:
+                    start_lr *= 0.1
+            for param_group in optimizer.param_groups:
+                param_group['lr'] = start_lr
+            print('Resumed optimizer with start lr', start_lr)
+        else:
+            print('No optimizer parameters in checkpoint.')
+    return model, optimizer, start_epoch
+
+
+def save_model(path, epoch, model, optimizer=None):
+    """reference model.py:92-101: ``{'epoch', 'state_dict'[, 'optimizer']}``"""
+    if isinstance(model, torch.nn.DataParallel):
+        state_dict = model.module.state_dict()
+    else:
+        state_dict = model.state_dict()
+    data = {'epoch': epoch, 'state_dict': state_dict}
+    if optimizer is not None:
+        data['optimizer'] = optimizer.state_dict()
+    torch.save(data, path)

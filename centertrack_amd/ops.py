@@ -1023,3 +1023,9 @@ def build_inputs(staging_host, staging_dev, nbytes, B, N, H, W, mean, std, image
     d.warped, d.partials = warped.data_ptr(), partials.data_ptr()
     d.gs_mean = gs_mean.data_ptr() if gs_mean is not None else None
     _lib.check(_lib.load().ct_build_inputs(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_inputs')
+
+
+def optim_step(table, n, chunks, kind):
+    """ct_optim_step (csrc/optim.hip) on the current stream: one launch over the ``n`` records and the chunk prefix of the
+    DEVICE int32 tensor ``table`` (``centertrack_amd.optim.pack`` lays it out, the caller has uploaded it)."""
+    _lib.check(_lib.load().ct_optim_step(table.data_ptr(), n, chunks, kind, _lib.stream_ptr()), 'ct_optim_step')

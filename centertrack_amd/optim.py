@@ -1,0 +1,376 @@
+"""The optimizer step on the device: ``Adam`` and ``SGD`` as drop-ins for ``torch.optim.Adam`` /
+``torch.optim.SGD`` -- the reference's two optimizers (src/main.py:17-26) -- whose ``step()`` updates every tensor of the
+optimizer with ONE launch of ``ct_optim_step`` (csrc/optim.hip).
+
+Both subclass the torch class and override ``step`` only: ``param_groups``, ``defaults``, ``zero_grad``,
+``add_param_group``, ``state_dict`` / ``load_state_dict`` and the reference's ``param_group['lr'] = lr`` schedule are
+torch's own, and the state is what torch creates (``step`` a float32 scalar tensor on the CPU, ``exp_avg``,
+``exp_avg_sq`` / ``momentum_buffer``), so a checkpoint's ``'optimizer'`` entry crosses both ways.
+
+``step()`` packs one record per tensor that has a gradient (``pack``) into a pinned block of the ``_staging`` ring,
+enqueues one asynchronous copy and one launch on the current stream and records the block's event: no host wait.  The
+bias corrections are formed on the host in double from each tensor's own integer step, as torch's non-capturable path
+forms them; a parameter whose ``.grad`` is ``None`` is skipped and its step does not advance.  A ``step`` tensor found
+on a device (``Trainer.set_device`` after ``load_state_dict``) is brought back to the CPU once: that one read waits.
+
+No CPU fallback: parameters, gradients and state must be CUDA float32 contiguous dense tensors, and ``amsgrad``,
+``maximize``, ``capturable``, ``differentiable``, ``decoupled_weight_decay``, ``nesterov``, ``dampening != 0`` and a
+tensor ``lr`` are refused with ``CTError``.  ``foreach`` / ``fused`` choose between torch's implementations and mean
+nothing here.
+"""
+import numpy as np
+import torch
+
+from . import _lib, _staging
+from ._lib import CTError
+
+CHUNK = _lib.CT_OPTIM_CHUNK                      # elements a workgroup updates per round (csrc/optim.hip)
+MAX_TENSORS = _lib.CT_OPTIM_MAX_TENSORS
+KINDS = {'adam': _lib.CT_OPTIM_ADAM, 'sgd': _lib.CT_OPTIM_SGD}
+# ct_optim_rec of include/centertrack_hip.h
+REC = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('numel', '<i8'),
+                ('s', '<f4', (_lib.CT_OPTIM_SCALARS,)), ('first', '<i4'), ('reserved', '<i4', (13,))])
+REC_WORDS = REC.itemsize // 4
+assert REC.itemsize == _lib.CT_OPTIM_REC_BYTES
+
+
+def adam_scalars(step, lr, beta1, beta2, eps, weight_decay):
+    """the seven scalars of an Adam record, in double (torch/optim/adam.py::_single_tensor_adam, non-capturable)"""
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    return (1 - beta1, beta2, 1 - beta2, lr / bias_correction1, bias_correction2 ** 0.5, eps, weight_decay)
+
+
+def table_words(n):
+    """int32 words of the table of ``n`` tensors: the records, then the chunk prefix"""
+    return n * REC_WORDS + n + 1
+
+
+def pack(kind, items, out=None):
+    """The table ``ct_optim_step`` reads, as int32 words: ``len(items)`` records, then the prefix of chunk starts.
+    ``items``: per tensor ``(p, g, m, v, numel, scalars, first)`` -- four device addresses (0: absent), the element
+    count, up to eight Python floats and the SGD flag.  ``out``: an int32 numpy array to fill instead of a fresh one.
+    Returns ``(words array, n, chunks)``.  Pure host code."""
+    if kind not in (_lib.CT_OPTIM_ADAM, _lib.CT_OPTIM_SGD):
+        raise CTError('optim.pack: kind %r is neither CT_OPTIM_ADAM nor CT_OPTIM_SGD' % (kind,))
+    n = len(items)
+    if n < 1 or n > MAX_TENSORS:
+        raise CTError('optim.pack: %d tensors outside [1, %d]' % (n, MAX_TENSORS))
+    p, g, m, v, numel, scalars, first = zip(*items)
+    rec = np.zeros(n, REC)
+    rec['p'], rec['g'], rec['m'], rec['v'], rec['numel'], rec['first'] = p, g, m, v, numel, first
+    s = np.asarray(scalars, np.float64)
+    if s.ndim != 2 or s.shape[1] > _lib.CT_OPTIM_SCALARS:
+        raise CTError('optim.pack: every tensor carries the same number (at most %d) of scalars' % _lib.CT_OPTIM_SCALARS)
+    rec['s'][:, :s.shape[1]] = s                 # double -> float32, rounded to nearest
+    null = (rec['p'] == 0) | (rec['g'] == 0)
+    if kind == _lib.CT_OPTIM_ADAM:
+        null |= (rec['m'] == 0) | (rec['v'] == 0)
+    if null.any():
+        raise CTError('optim.pack: null pointer in a record')
+    if ((rec['p'] | rec['g'] | rec['m'] | rec['v']) & 3).any():
+        raise CTError('optim.pack: a pointer that is not 4-byte aligned')
+    if (rec['numel'] <= 0).any():
+        raise CTError('optim.pack: a tensor without elements')
+    prefix = np.zeros(n + 1, np.int64)
+    np.cumsum((rec['numel'] + (CHUNK - 1)) // CHUNK, out=prefix[1:])
+    if prefix[-1] >= 1 << 31:
+        raise CTError('optim.pack: %d chunks do not fit one launch' % prefix[-1])
+    words = table_words(n)
+    if out is None:
+        out = np.empty(words, np.int32)
+    elif out.dtype != np.int32 or out.ndim != 1 or out.size < words:
+        raise CTError('optim.pack: out must be an int32 vector of at least %d words' % words)
+    out[:n * REC_WORDS] = rec.view(np.int32)
+    out[n * REC_WORDS:words] = prefix
+    return out, n, int(prefix[-1])
+
+
+def find_tensor(prefix, chunk):
+    """the binary search of optim_step_kernel: the tensor t with prefix[t] <= chunk < prefix[t + 1]"""
+    lo, hi = 0, len(prefix) - 1
+    while hi - lo > 1:
+        mid = (lo + hi) >> 1
+        if prefix[mid] <= chunk:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+_FMA = {}
+
+
+def _fma(a, b, c, fused):
+    """``a * b + c`` on numpy arrays of one dtype: rounded once when ``fused`` (libm's fma / fmaf, element by element --
+    sizes of a test), product and sum rounded separately otherwise"""
+    if not fused:
+        return a * b + c
+    dtype = np.result_type(a, b, c)
+    if dtype not in _FMA:
+        import ctypes
+        import ctypes.util
+        libm = ctypes.CDLL(ctypes.util.find_library('m') or 'libm.so.6')
+        fn, ct = (libm.fma, ctypes.c_double) if dtype == np.float64 else (libm.fmaf, ctypes.c_float)
+        fn.restype, fn.argtypes = ct, [ct] * 3
+        _FMA[dtype] = np.frompyfunc(fn, 3, 1)
+    return _FMA[dtype](a, b, c).astype(dtype)
+
+
+def reference_step(kind, p, g, state, hyper, fused=None):
+    """One step of torch's single-tensor Adam / SGD (``foreach=False``) on numpy arrays, in ``p``'s dtype (float64 or
+    float32), as torch's CPU kernels compute it: the scalars are formed in double and rounded to that dtype; the
+    operations come in the kernels' order.  ``p`` and ``state`` (``{}`` before the first step; ``step`` an int) are
+    updated in place.  ``hyper``: ``lr``, ``betas``, ``eps``, ``weight_decay`` / ``lr``, ``momentum``, ``weight_decay``.
+    For the tests.
+
+    Two things of those kernels are not plain IEEE operation by operation.  ``fused`` (default: whether torch dispatches
+    to its AVX2 / AVX-512 kernels on this CPU): ``add(alpha)``, ``lerp`` and ``addcmul`` round their last product and sum
+    once there (a fused multiply-add).  And the square root is torch's own: its vectorised CPU square root is not
+    correctly rounded (it differs from numpy's in 0.7% of float64 values), so no restatement reproduces it.
+    The device kernel (csrc/optim.hip) fuses nothing, rounds division and square root correctly and forms
+    ``-step_size (m / denom)`` where the CPU kernel forms ``(-step_size m) / denom``."""
+    if fused is None:
+        fused = torch.backends.cpu.get_cpu_capability() != 'DEFAULT'
+    dt = p.dtype.type
+    g = np.asarray(g, p.dtype)
+    wd = hyper.get('weight_decay', 0)
+    if kind == 'adam':
+        if not state:
+            state.update(step=0, exp_avg=np.zeros_like(p), exp_avg_sq=np.zeros_like(p))
+        state['step'] += 1
+        b1, b2 = hyper.get('betas', (0.9, 0.999))
+        omb1, b2, omb2, step_size, bc2_sqrt, eps, wd = (
+            dt(x) for x in adam_scalars(state['step'], hyper['lr'], b1, b2, hyper.get('eps', 1e-8), wd))
+        if wd != 0:
+            g = _fma(p, wd, g, fused)
+        m, v = state['exp_avg'], state['exp_avg_sq']
+        m[...] = _fma(omb1, g - m, m, fused)
+        v *= b2
+        v[...] = _fma(omb2 * g, g, v, fused)
+        denom = torch.from_numpy(np.ascontiguousarray(v)).sqrt().numpy() / bc2_sqrt + eps
+        p += (-step_size * m) / denom
+    elif kind == 'sgd':
+        lr, mom, wd = dt(hyper['lr']), dt(hyper.get('momentum', 0)), dt(wd)
+        if wd != 0:
+            g = _fma(p, wd, g, fused)
+        if mom != 0:
+            if 'momentum_buffer' not in state:
+                state['momentum_buffer'] = np.array(g, copy=True)
+            else:
+                buf = state['momentum_buffer']
+                buf *= mom
+                buf += g
+            g = state['momentum_buffer']
+        p[...] = _fma(g, -lr, p, fused)
+    else:
+        raise CTError('optim.reference_step: kind %r is neither "adam" nor "sgd"' % (kind,))
+
+
+def _check_tensor(t, like, what, who):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.layout == torch.strided
+            and t.is_contiguous()):
+        got = '%s %s %s' % (t.device, t.dtype, t.layout) if torch.is_tensor(t) else type(t).__name__
+        raise CTError('%s: %s must be a CUDA float32 contiguous dense tensor (got %s); no CPU fallback' % (who, what, got))
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise CTError('%s: %s of shape %s on %s for a parameter of shape %s on %s'
+                      % (who, what, tuple(t.shape), t.device, tuple(like.shape), like.device))
+
+
+class _FusedStep(object):
+    """what ``Adam`` and ``SGD`` share: the refusals and the launch"""
+    _kind = None
+    _refused = ()                                # group keys that must be falsy
+
+    def _check_group(self, group):
+        who = type(self).__name__
+        for k in self._refused:
+            if group.get(k):
+                raise CTError('centertrack_amd.optim.%s: %s=%r is not supported' % (who, k, group[k]))
+        if torch.is_tensor(group['lr']):
+            raise CTError('centertrack_amd.optim.%s: a tensor lr is not supported (a Python float is)' % who)
+
+    # What step() knows about a parameter from its last visit: [p address, numel, device, the state tensors (identity),
+    # their addresses, (Adam) the step tensor, its version counter and its value as an int].  A visit re-reads the
+    # parameter's address and compares the state tensors by identity; anything else -- first visit, ``p.data = ...``,
+    # ``load_state_dict``, ``Trainer.set_device`` -- goes through the full checks of ``_admit`` again.
+    def _gradient(self, p):
+        g = p.grad
+        if g is not None and (g.layout is not torch.strided or not g.is_contiguous()):
+            raise CTError('centertrack_amd.optim.%s: a gradient must be a contiguous dense tensor (got %s, strides %s); '
+                          'no CPU fallback' % (type(self).__name__, g.layout, g.stride() if g.layout is torch.strided else '-'))
+        return g
+
+    def _advance(self, visited):
+        """``step += 1`` for every visited tensor in one call, as torch's float32 scalars on the CPU"""
+        if visited:
+            torch._foreach_add_([c[5] for c in visited], 1)
+            for c in visited:
+                c[6] = c[5]._version
+
+    def _launch(self, per_device):
+        from . import ops
+        ring = self.__dict__.setdefault('_ring', [])
+        for device, items in per_device.items():
+            words = table_words(len(items))
+            entry = _staging.take(ring, words, torch.int32)
+            _, n, chunks = pack(self._kind, items, out=entry['host'].numpy())
+            with torch.cuda.device(device):
+                table = torch.empty(words, dtype=torch.int32, device=device)
+                table.copy_(entry['host'][:words], non_blocking=True)
+                ops.optim_step(table, n, chunks, self._kind)
+                entry['event'].record()
+
+    @staticmethod
+    def _closure(closure):
+        if closure is None:
+            return None
+        with torch.enable_grad():
+            return closure()
+
+
+class Adam(_FusedStep, torch.optim.Adam):
+    """``torch.optim.Adam`` with the step on ``ct_optim_step``"""
+    _kind = _lib.CT_OPTIM_ADAM
+    _refused = ('amsgrad', 'maximize', 'capturable', 'differentiable', 'decoupled_weight_decay')
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        for k, v in (('amsgrad', amsgrad), ('maximize', maximize), ('capturable', capturable),
+                     ('differentiable', differentiable), ('decoupled_weight_decay', decoupled_weight_decay)):
+            if v:
+                raise CTError('centertrack_amd.optim.Adam: %s=%r is not supported' % (k, v))
+        if torch.is_tensor(lr):
+            raise CTError('centertrack_amd.optim.Adam: a tensor lr is not supported (a Python float is)')
+        torch.optim.Adam.__init__(self, params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                                  foreach=foreach, maximize=maximize, capturable=capturable,
+                                  differentiable=differentiable, fused=fused,
+                                  decoupled_weight_decay=decoupled_weight_decay)
+
+    def _admit(self, p, g, state):
+        who = 'centertrack_amd.optim.Adam'
+        _check_tensor(p, None, 'a parameter', who)
+        _check_tensor(g, p, 'a gradient', who)
+        if p.numel() == 0:
+            return None
+        if len(state) == 0:
+            state['step'] = torch.tensor(0.0, dtype=torch.float32)
+            state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        m, v, st = state['exp_avg'], state['exp_avg_sq'], state['step']
+        _check_tensor(m, p, 'exp_avg', who)
+        _check_tensor(v, p, 'exp_avg_sq', who)
+        if st.device.type != 'cpu':                  # (one read that waits; torch keeps this scalar on the CPU)
+            st = state['step'] = st.cpu()
+        return [p.data_ptr(), p.numel(), p.device, m, v, st, st._version, int(st), m.data_ptr(), v.data_ptr()]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = self._closure(closure)
+        cache = self.__dict__.setdefault('_cache', {})
+        per_device, visited = {}, []
+        try:
+            for group in self.param_groups:
+                self._check_group(group)
+                beta1, beta2 = group['betas']
+                if torch.is_tensor(beta1) or torch.is_tensor(beta2):
+                    raise CTError('centertrack_amd.optim.Adam: tensor betas are not supported')
+                lr, eps, wd = group['lr'], group['eps'], group['weight_decay']
+                scalars = {}
+                for p in group['params']:
+                    g = self._gradient(p)
+                    if g is None:
+                        continue
+                    c, state, ptr = cache.get(p), self.state[p], p.data_ptr()
+                    if (c is None or c[0] != ptr or state.get('exp_avg') is not c[3] or state.get('exp_avg_sq') is not c[4]
+                            or state.get('step') is not c[5] or c[5]._version != c[6]):
+                        c = cache[p] = self._admit(p, g, state)
+                        if c is None:
+                            continue
+                    t = c[7] = c[7] + 1
+                    visited.append(c)
+                    if t not in scalars:
+                        scalars[t] = adam_scalars(t, lr, beta1, beta2, eps, wd)
+                    per_device.setdefault(c[2], []).append((c[0], g.data_ptr(), c[8], c[9], c[1], scalars[t], 0))
+            self._advance(visited)
+        except BaseException:
+            cache.clear()
+            raise
+        self._launch(per_device)
+        return loss
+
+
+class SGD(_FusedStep, torch.optim.SGD):
+    """``torch.optim.SGD`` (momentum, weight decay) with the step on ``ct_optim_step``"""
+    _kind = _lib.CT_OPTIM_SGD
+    _refused = ('nesterov', 'dampening', 'maximize', 'differentiable')
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 foreach=None, differentiable=False, fused=None):
+        for k, v in (('nesterov', nesterov), ('dampening', dampening), ('maximize', maximize),
+                     ('differentiable', differentiable)):
+            if v:
+                raise CTError('centertrack_amd.optim.SGD: %s=%r is not supported' % (k, v))
+        if torch.is_tensor(lr) or torch.is_tensor(weight_decay):
+            raise CTError('centertrack_amd.optim.SGD: a tensor lr / weight_decay is not supported (a Python float is)')
+        torch.optim.SGD.__init__(self, params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                 nesterov=nesterov, maximize=maximize, foreach=foreach, differentiable=differentiable,
+                                 fused=fused)
+
+    def _admit(self, p, g, state, momentum):
+        who = 'centertrack_amd.optim.SGD'
+        _check_tensor(p, None, 'a parameter', who)
+        _check_tensor(g, p, 'a gradient', who)
+        if p.numel() == 0:
+            return None
+        buf, first = None, 0
+        if momentum != 0:
+            buf = state.get('momentum_buffer')
+            if buf is None:
+                buf = state['momentum_buffer'] = torch.empty_like(p, memory_format=torch.preserve_format)
+                first = 1                            # the kernel writes it: buf = grad
+            _check_tensor(buf, p, 'momentum_buffer', who)
+        return [p.data_ptr(), p.numel(), p.device, buf, buf.data_ptr() if buf is not None else 0, first]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = self._closure(closure)
+        cache = self.__dict__.setdefault('_cache', {})
+        per_device = {}
+        try:
+            for group in self.param_groups:
+                self._check_group(group)
+                lr, momentum, wd = group['lr'], group['momentum'], group['weight_decay']
+                if torch.is_tensor(wd):
+                    raise CTError('centertrack_amd.optim.SGD: a tensor weight_decay is not supported')
+                scalars = (lr, momentum, wd)
+                for p in group['params']:
+                    g = self._gradient(p)
+                    if g is None:
+                        continue
+                    c, ptr = cache.get(p), p.data_ptr()
+                    # (torch keeps no state at all without momentum: self.state[p] is not touched then)
+                    buf = self.state[p].get('momentum_buffer') if momentum != 0 else None
+                    if c is None or c[0] != ptr or buf is not c[3] or buf is None and momentum != 0:
+                        c = cache[p] = self._admit(p, g, self.state[p] if momentum != 0 else None, momentum)
+                        if c is None:
+                            continue
+                    per_device.setdefault(c[2], []).append((c[0], g.data_ptr(), c[4], 0, c[1], scalars, c[5]))
+                    c[5] = 0
+        except BaseException:
+            cache.clear()
+            raise
+        self._launch(per_device)
+        return loss
+
+
+def get_optimizer(opt, model):
+    """the reference's src/main.py:17-26 with the classes above"""
+    if opt.optim == 'adam':
+        optimizer = Adam(model.parameters(), opt.lr)
+    elif opt.optim == 'sgd':
+        print('Using SGD')
+        optimizer = SGD(model.parameters(), opt.lr, momentum=0.9, weight_decay=0.0001)
+    else:
+        assert 0, opt.optim
+    return optimizer

@@ -1,0 +1,134 @@
+"""The reference's training loop (src/lib/trainer.py:89-189) around this package's modules, without its per-iteration host
+waits.
+
+``Trainer(opt, model, optimizer)`` with ``set_device``, ``train`` / ``val`` / ``run_epoch`` returning the reference's
+``(ret, results)``: ``ret[l]`` the batch-size-weighted average of ``loss_stats[l].mean()`` for ``'tot'`` and every head
+with ``opt.weights[l] > 0``, and ``ret['time']`` in minutes.  The reference reads every loss statistic back with
+``.item()`` on every iteration; here the sums stay on the device -- float64, ``sum += val * n`` in the reference's order, so
+the averages are the ``AverageMeter``'s to the bit -- and the host reads them every ``opt.print_iter`` iterations (when
+> 0) and once at the end of the epoch.  The model is any ``model(image, pre_img, pre_hm) -> [ {head: logits} ]`` of this
+package (``dla_seg.DLASeg``, ``heads.HeadFinetuner``), the loss is ``losses.GenericLoss``, the optimizer either
+``centertrack_amd.optim``'s or torch's.
+
+Not covered: more than one GPU (``DataParallel``), ``opt.debug > 0`` (the reference's drawing), the progress bar (a plain
+line is printed instead).
+"""
+import time
+
+import torch
+
+from . import dcn_v2
+from ._lib import CTError
+from .losses import GenericLoss
+
+LOSS_ORDER = ('hm', 'wh', 'reg', 'ltrb', 'hps', 'hm_hp', 'hp_offset', 'dep', 'dim', 'rot', 'amodel_offset', 'ltrb_amodal',
+              'tracking', 'nuscenes_att', 'velocity')
+
+
+class ModelWithLoss(torch.nn.Module):
+    """the reference's ``ModleWithLoss``: ``forward(batch) -> (outputs[-1], loss, loss_stats)``"""
+
+    def __init__(self, model, loss):
+        super().__init__()
+        self.model = model
+        self.loss = loss
+
+    def forward(self, batch):
+        pre_img = batch['pre_img'] if 'pre_img' in batch else None
+        pre_hm = batch['pre_hm'] if 'pre_hm' in batch else None
+        outputs = self.model(batch['image'], pre_img, pre_hm)
+        loss, loss_stats = self.loss(outputs, batch)
+        return outputs[-1], loss, loss_stats
+
+
+class Trainer(object):
+    def __init__(self, opt, model, optimizer=None):
+        self._refuse_debug(opt)
+        self.opt = opt
+        self.optimizer = optimizer
+        self.loss_stats, self.loss = self._get_losses(opt)
+        self.model_with_loss = ModelWithLoss(model, self.loss)
+        self.device = getattr(opt, 'device', None)
+
+    @staticmethod
+    def _refuse_debug(opt):
+        if getattr(opt, 'debug', 0) > 0:
+            raise CTError('centertrack_amd.trainer.Trainer: opt.debug = %r is not supported (the reference draws its '
+                          'detections there)' % (opt.debug,))
+
+    def set_device(self, gpus, chunk_sizes, device):
+        if len(gpus) > 1:
+            raise CTError('centertrack_amd.trainer.Trainer runs on one GPU (gpus = %s): DataParallel is not covered'
+                          % (list(gpus),))
+        self.device = device
+        self.model_with_loss = self.model_with_loss.to(device)
+        if self.optimizer is not None:
+            for state in self.optimizer.state.values():
+                for k, v in state.items():
+                    if isinstance(v, torch.Tensor):
+                        state[k] = v.to(device=device, non_blocking=True)
+
+    def _get_losses(self, opt):
+        loss_states = ['tot'] + [k for k in LOSS_ORDER if k in opt.heads]
+        return loss_states, GenericLoss(opt)
+
+    def run_epoch(self, phase, epoch, data_loader):
+        opt = self.opt
+        self._refuse_debug(opt)
+        train = phase == 'train'
+        if train and self.optimizer is None:
+            raise CTError('centertrack_amd.trainer.Trainer: the train phase needs an optimizer')
+        model_with_loss = self.model_with_loss
+        if train:
+            model_with_loss.train()
+        else:
+            model_with_loss.eval()
+            torch.cuda.empty_cache()
+        device = self.device
+        results = {}
+        names = [l for l in self.loss_stats if l == 'tot' or opt.weights[l] > 0]
+        num_iters = len(data_loader) if opt.num_iters < 0 else opt.num_iters
+        print_iter = getattr(opt, 'print_iter', 0)
+        title = '{}/{}'.format(getattr(opt, 'task', ''), getattr(opt, 'exp_id', ''))
+        sums, count, done = None, 0, 0
+        start = time.time()
+
+        def line(host_sums):
+            text = '{}| {}: [{}][{}/{}]|Tot: {:.1f}s '.format(title, phase, epoch, done, num_iters, time.time() - start)
+            for l, s in zip(names, host_sums):
+                text += '|{} {:.4f} '.format(l, s / count if count else 0.0)
+            return text
+
+        with dcn_v2.trainable(train or dcn_v2.is_trainable()):
+            for iter_id, batch in enumerate(data_loader):
+                if iter_id >= num_iters:
+                    break
+                for k in batch:
+                    if k != 'meta':
+                        batch[k] = batch[k].to(device=device, non_blocking=True)
+                output, loss, loss_stats = model_with_loss(batch)
+                loss = loss.mean()
+                if train:
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    self.optimizer.step()
+                # AverageMeter.update(val, n) for every statistic at once, on the device: sum += val * n in double
+                n = batch['image'].size(0)
+                vals = torch.stack([loss_stats[l].detach().mean().double() for l in names])
+                sums = vals * n if sums is None else sums + vals * n
+                count += n
+                done = iter_id + 1
+                if print_iter > 0 and iter_id % print_iter == 0:
+                    print(line(sums.cpu().tolist()))                      # the only per-iteration read, on request
+                del output, loss, loss_stats
+        host_sums = sums.cpu().tolist() if sums is not None else [0.0] * len(names)   # waits for the epoch's last launch
+        ret = {l: (s / count if count else 0) for l, s in zip(names, host_sums)}
+        ret['time'] = (time.time() - start) / 60.
+        print(line(host_sums))
+        return ret, results
+
+    def val(self, epoch, data_loader):
+        return self.run_epoch('val', epoch, data_loader)
+
+    def train(self, epoch, data_loader):
+        return self.run_epoch('train', epoch, data_loader)

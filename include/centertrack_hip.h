@@ -934,6 +934,44 @@ typedef struct ct_inputs_desc {
 size_t ct_build_inputs_partials(int H, int W);          /* partial sums per image; 0 on bad sizes */
 int ct_build_inputs(const ct_inputs_desc *d, void *stream);
 
+/* ---- fused optimizer step (an addition under ABI 103) ------------------------------------
+ * torch.optim.Adam / torch.optim.SGD (the reference's two optimizers, src/main.py:17-26) for EVERY tensor of an
+ * optimizer in ONE launch, whatever their number, sizes and parameter groups.  `table` is a DEVICE buffer the caller
+ * has uploaded (centertrack_amd/optim.py packs it): n records of CT_OPTIM_REC_BYTES bytes, then n + 1 int32 words,
+ * prefix[t] = number of CT_OPTIM_CHUNK-element chunks of the tensors before t (prefix[0] = 0, prefix[n] = all chunks).
+ * A workgroup takes chunks c, c + grid, ..: it finds c's tensor by binary search in the prefix and updates elements
+ * [(c - prefix[t]) * CT_OPTIM_CHUNK, ..) of it -- with 16-byte loads and stores when p, g, m, v are all 16-byte
+ * aligned, element by element otherwise and for the last numel % 4 elements.  Every element of p, m, v is read once
+ * and written once, nothing outside [ptr, ptr + numel) is touched; no atomics, no LDS, no workspace.
+ * The scalars are per tensor and float32, formed by the host in double from the tensor's own integer step t:
+ *   Adam  s[0] 1 - beta1, s[1] beta2, s[2] 1 - beta2, s[3] lr / (1 - beta1^t), s[4] sqrt(1 - beta2^t), s[5] eps,
+ *         s[6] weight_decay:    g' = g + wd p (wd != 0);  m += s0 (g' - m);  v = s1 v + (s2 g') g';
+ *                               p += -s3 (m / (sqrt(v) / s4 + s5))
+ *   SGD   s[0] lr, s[1] momentum, s[2] weight_decay; first != 0: the buffer is created by this step:
+ *                               g' = g + wd p (wd != 0);  m = first ? g' : s1 m + g';  p += -s0 m
+ *         (m NULL: no momentum, p += -s0 g')
+ * in float32 in this order, without contraction, division and square root correctly rounded (the non-capturable
+ * branch of torch/optim/adam.py::_single_tensor_adam and torch/optim/sgd.py::_single_tensor_sgd).
+ * CT_ERR_ARG before anything is enqueued: a null table, n outside [1, CT_OPTIM_MAX_TENSORS], chunks outside
+ * [n, 2^31), a kind outside the enum.  `chunks` (= prefix[n]) only sizes the grid: the kernel reads the prefix. */
+#define CT_OPTIM_ADAM 0
+#define CT_OPTIM_SGD 1
+#define CT_OPTIM_CHUNK 4096
+#define CT_OPTIM_REC_BYTES 128
+#define CT_OPTIM_SCALARS 8
+#define CT_OPTIM_MAX_TENSORS (1 << 20)
+typedef struct ct_optim_rec {
+    float *p;                       /* DEVICE fp32 [numel], updated in place */
+    const float *g;                 /* gradient */
+    float *m;                       /* exp_avg / momentum_buffer */
+    float *v;                       /* exp_avg_sq (Adam; NULL for SGD) */
+    long long numel;                /* > 0 */
+    float s[CT_OPTIM_SCALARS];
+    int first;                      /* SGD: this step creates the momentum buffer */
+    int reserved[13];
+} ct_optim_rec;
+int ct_optim_step(const void *table, int n, long long chunks, int kind, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
