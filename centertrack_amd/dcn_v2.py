@@ -27,13 +27,13 @@ changed by any means between two calls -- an optimizer step, ``load_state_dict``
 ``.data`` (``m.weight.data.mul_(2)``, ``w = m.weight.data; w[...] = ...``, as the reference's ``fill_up_weights`` and
 many checkpoint loaders do), which does not advance the parameter's version counter -- and the next call uses it.
 """
-import contextlib
 import math
 
 import torch
 from torch import nn
 
 from . import _lib, ops
+from ._train import is_trainable, need_cuda, recording, set_trainable, trainable  # noqa: F401  (the switch is public API here)
 
 
 def _check_geometry(kernel_size, stride, padding, dilation, deformable_groups, cin):
@@ -49,13 +49,6 @@ def _check_geometry(kernel_size, stride, padding, dilation, deformable_groups, c
         raise _lib.CTError('centertrack_amd DCN needs in_channels %% 32 == 0 (got %d)' % cin)
 
 
-def _need_cuda(x):
-    if not x.is_cuda:
-        raise _lib.CTError('centertrack_amd DCN runs on an MI355X only (got a %s tensor); no CPU fallback' % x.device)
-    if x.dtype != torch.float32:
-        raise _lib.CTError('centertrack_amd DCN computes in fp32 (got %s)' % x.dtype)
-
-
 def _om_view(offset, mask):
     """NCHW offset [B,18,H,W] + mask [B,9,H,W] -> the kernel's NHWC offset/mask map [B,H,W,32]"""
     B, _, H, W = offset.shape
@@ -67,33 +60,15 @@ def _om_view(offset, mask):
     return ops.View(om.buf, 0, 27)
 
 
-_trainable = False
-
-
-def set_trainable(flag):
-    """Switch the differentiable path of ``dcn_v2_conv`` / ``DCNv2`` / ``DCN`` on or off (default: off).  Returns the
-    previous setting.  Off, every call is today's inference call whatever ``requires_grad`` or ``module.training`` say."""
-    global _trainable
-    was = _trainable
-    _trainable = bool(flag)
-    return was
-
-
-def is_trainable():
-    return _trainable
-
-
-@contextlib.contextmanager
-def trainable(flag=True):
-    was = set_trainable(flag)
-    try:
-        yield
-    finally:
-        set_trainable(was)
-
-
-def _differentiable():
-    return _trainable and torch.is_grad_enabled()
+def _forward(input, offset, mask, weight, bias, wp):
+    """The drop-in's forward on NCHW tensors -> (out view, x view, om view).  ``wp``: the fragment packing of ``weight``, or
+    None to make it here"""
+    x = ops.view_from_nchw(input)
+    om = _om_view(offset.float(), mask.float())
+    if wp is None:
+        wp = ops.pack_weight(weight.detach())
+    out = ops.dcn_v2(x, om, wp, weight.shape[0], shift=None if bias is None else bias.detach().contiguous())
+    return out, x, om
 
 
 class _DCNv2Function(torch.autograd.Function):
@@ -103,11 +78,9 @@ class _DCNv2Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, offset, mask, weight, bias, packs):
-        x = ops.view_from_nchw(input)
-        om = _om_view(offset.float(), mask.float())
-        wp, wT = packs if packs is not None else (ops.pack_weight(weight.detach()), None)
-        out = ops.dcn_v2(x, om, wp, weight.shape[0], shift=None if bias is None else bias.detach().contiguous())
-        ctx.x, ctx.om, ctx.wT = x, om, wT
+        wp, wT = packs if packs is not None else (None, None)
+        out, ctx.x, ctx.om = _forward(input, offset, mask, weight, bias, wp)
+        ctx.wT = wT
         ctx.has_bias = bias is not None
         ctx.save_for_backward(weight)
         return ops.view_to_nchw(out)
@@ -132,20 +105,16 @@ class _DCNv2Function(torch.autograd.Function):
 def dcn_v2_conv(input, offset, mask, weight, bias, stride=1, padding=1, dilation=1, deformable_groups=1):
     """Upstream ``dcn_v2_conv = _DCNv2.apply``.  offset [B,18,H,W] with (dy,dx) interleaved per tap, mask [B,9,H,W]
     (already sigmoid-ed), weight [Co,Ci,3,3], bias [Co].  Differentiable under ``trainable()``."""
-    _need_cuda(input)
+    need_cuda(input, 'centertrack_amd DCN', dims=None)
     _check_geometry(tuple(weight.shape[2:]), stride, padding, dilation, deformable_groups, input.shape[1])
-    if _differentiable():
+    if recording():
         return _DCNv2Function.apply(input, offset, mask, weight, bias, None)
     return _dcn_v2_conv_inference(input, offset, mask, weight, bias)
 
 
 @torch.no_grad()
 def _dcn_v2_conv_inference(input, offset, mask, weight, bias):
-    x = ops.view_from_nchw(input)
-    om = _om_view(offset.float(), mask.float())
-    wp = ops.pack_weight(weight.detach())
-    out = ops.dcn_v2(x, om, wp, weight.shape[0], shift=None if bias is None else bias.detach().contiguous())
-    return ops.view_to_nchw(out)
+    return ops.view_to_nchw(_forward(input, offset, mask, weight, bias, None)[0])
 
 
 class DCNv2(nn.Module):
@@ -176,17 +145,14 @@ class DCNv2(nn.Module):
         return ops.pack_weight(w), ops.pack_weight_t(w)
 
     def forward(self, input, offset, mask):
-        _need_cuda(input)
-        if _differentiable():
+        need_cuda(input, 'centertrack_amd DCN', dims=None)
+        if recording():
             return _DCNv2Function.apply(input, offset, mask, self.weight, self.bias, self._packs())
         return self._forward_inference(input, offset, mask)
 
     @torch.no_grad()
     def _forward_inference(self, input, offset, mask):
-        x = ops.view_from_nchw(input)
-        om = _om_view(offset.float(), mask.float())
-        out = ops.dcn_v2(x, om, ops.pack_weight(self.weight.detach()), self.out_channels, shift=self.bias.detach())
-        return ops.view_to_nchw(out)
+        return ops.view_to_nchw(_forward(input, offset, mask, self.weight, self.bias, None)[0])
 
 
 class DCN(DCNv2):
@@ -205,8 +171,8 @@ class DCN(DCNv2):
         self.conv_offset_mask.bias.data.zero_()
 
     def forward(self, input):
-        _need_cuda(input)
-        if _differentiable():
+        need_cuda(input, 'centertrack_amd DCN', dims=None)
+        if recording():
             # as upstream: the offset/mask conv, chunk / cat / sigmoid in torch (their backward is torch's), the
             # deformable conv through the Function
             out = self.conv_offset_mask(input)

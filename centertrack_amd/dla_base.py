@@ -30,8 +30,8 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib, ops
-from .dla_up import BN_MOMENTUM, _recording, _ToNCHW, _ToNHWC, update_running_stats
+from . import _lib, _train, ops
+from ._train import BN_MOMENTUM, bn_statistics, need_cuda, recording, saved_mean, to_nchw
 from .ops import View
 
 # None = off; a list receives, in call order, the NHWC output of every conv-BN-act unit, of every pool and of every stem
@@ -44,31 +44,8 @@ def _emit(t):
         trace.append(t.detach())
 
 
-def _need_cuda(x, what='backbone'):
-    if not x.is_cuda:
-        raise _lib.CTError('centertrack_amd %s runs on an MI355X only (got a %s tensor); no CPU fallback' % (what, x.device))
-    if x.dtype != torch.float32:
-        raise _lib.CTError('centertrack_amd %s computes in fp32 (got %s)' % (what, x.dtype))
-    if x.dim() != 4:
-        raise _lib.CTError('centertrack_amd %s wants a 4-d tensor (got %s)' % (what, tuple(x.shape)))
-
-
 def to_nhwc(x):
-    """NCHW fp32 CUDA tensor -> contiguous ``[N,H,W,C]`` tensor (differentiable while a graph is recorded)"""
-    _need_cuda(x)
-    if x.shape[1] % 4:
-        raise _lib.CTError('centertrack_amd backbone needs channels %% 4 == 0 (got %d)' % x.shape[1])
-    if _recording():
-        return _ToNHWC.apply(x)
-    with torch.no_grad():
-        return ops.view_from_nchw(x).buf
-
-
-def to_nchw(x):
-    if _recording():
-        return _ToNCHW.apply(x)
-    with torch.no_grad():
-        return ops.view_to_nchw(View(x))
+    return _train.to_nhwc(x, 'backbone')
 
 
 def _check_channels(*cs):
@@ -89,16 +66,7 @@ def _unit_forward(x, conv, bn, res, relu, pool):
         raise _lib.CTError('centertrack_amd backbone: a stride-2 level needs even H and W (got %d x %d)' % (x.H, x.W))
     z = ops.conv2d(x, ops.pack_weight(conv.weight.detach()), conv.out_channels, ks, stride)
     pooled = ops.maxpool2x2(x) if pool else None
-    batch = bn.training or bn.running_mean is None
-    if batch:
-        P = z.N * z.H * z.W
-        if P == 1:
-            raise _lib.CTError('backbone: training-mode BatchNorm needs more than one value per channel (N*H*W == 1)')
-        mean, var, invstd = ops.bn_stats(z, bn.eps)
-        if bn.training and bn.running_mean is not None:
-            update_running_stats(bn, mean, var, P)
-    else:
-        mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+    mean, invstd, batch = bn_statistics(bn, z, 'backbone')
     y = ops.bn_act_apply(z, mean, invstd, bn.weight.detach(), bn.bias.detach(), res=res, relu=relu)
     return y, pooled, (z, mean, invstd, batch)
 
@@ -114,7 +82,7 @@ class _ConvBnActFunction(torch.autograd.Function):
         # z, mean and invstd are kept on ctx, not through save_for_backward: they are private to this call (z and the batch
         # statistics are allocated here, running statistics are cloned), nobody else holds them, so there is no in-place write
         # for autograd's version check to catch
-        ctx.z, ctx.mean, ctx.invstd, ctx.batch = z, mean if batch else mean.clone(), invstd, batch
+        ctx.z, ctx.mean, ctx.invstd, ctx.batch = z, saved_mean(mean, batch), invstd, batch
         ctx.relu, ctx.pool, ctx.ks, ctx.stride = relu, pool, conv.kernel_size[0], conv.stride[0]
         ctx.save_for_backward(x, weight, gamma, beta, res)
         ctx.set_materialize_grads(False)
@@ -143,9 +111,7 @@ class _ConvBnActFunction(torch.autograd.Function):
                 if need_w:
                     gw, _ = ops.conv_backward_weight(xv, gz, ctx.ks, need_bias=False)
                 if need_x:
-                    # conv(gz, w^T): wT[ci, co, ky, kx] = w[co, ci, ks - 1 - ky, ks - 1 - kx], on the forward conv kernels
-                    wt = weight.detach().permute(1, 0, 2, 3).flip(2, 3).contiguous()
-                    gx = ops.conv2d(gz, ops.pack_weight(wt), xv.C, ctx.ks, 1)
+                    gx = ops.conv_backward_input(gz, weight.detach())
         if ctx.pool and gpool is not None and need_x:
             gx = ops.maxpool2x2_backward(xv, View(gpool.contiguous()), add=gx)
         return (gx.buf if gx is not None else None, gw, gg, gb, gres, None, None, None, None)
@@ -170,7 +136,7 @@ def _conv_bn_act(x, conv, bn, res=None, relu=True, pool=False):
     """The unit on ``[N,H,W,C]`` tensors; with ``pool`` -> (y, the 2x2 max-pool of ``x``)"""
     x = x.contiguous()
     res = None if res is None else res.contiguous()
-    if _recording():
+    if recording():
         out = _ConvBnActFunction.apply(x, conv.weight, bn.weight, bn.bias, res, conv, bn, relu, pool)
     else:
         with torch.no_grad():
@@ -185,7 +151,7 @@ def _maxpool(x):
     x = x.contiguous()
     if x.shape[1] % 2 or x.shape[2] % 2:
         raise _lib.CTError('centertrack_amd backbone: the 2x2 max-pool needs even H and W (got %d x %d)' % (x.shape[1], x.shape[2]))
-    if _recording():
+    if recording():
         y = _MaxPoolFunction.apply(x)
     else:
         with torch.no_grad():
@@ -204,18 +170,7 @@ def _stems_forward(inputs, layers):
     zs = ops.stem_conv_forward(inputs, [None if layers[s] is None else layers[s][0].weight.detach() for s in range(3)])
     means, invstds, batches = [None] * 3, [None] * 3, [False] * 3
     for s in live:
-        bn, z = layers[s][1], zs[s]
-        batch = bn.training or bn.running_mean is None
-        if batch:
-            P = z.N * z.H * z.W
-            if P == 1:
-                raise _lib.CTError('backbone: training-mode BatchNorm needs more than one value per channel (N*H*W == 1)')
-            mean, var, invstd = ops.bn_stats(z, bn.eps)
-            if bn.training and bn.running_mean is not None:
-                update_running_stats(bn, mean, var, P)
-        else:
-            mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
-        means[s], invstds[s], batches[s] = mean, invstd, batch
+        means[s], invstds[s], batches[s] = bn_statistics(layers[s][1], zs[s], 'backbone')
     gammas = [layers[s][1].weight.detach() if s in live else None for s in range(3)]
     betas = [layers[s][1].bias.detach() if s in live else None for s in range(3)]
     if trace is not None:
@@ -236,7 +191,7 @@ class _StemsFunction(torch.autograd.Function):
         inputs = (x, pre_img, pre_hm)
         y, (zs, means, invstds, batches) = _stems_forward(inputs, layers)
         ctx.zs, ctx.invstds, ctx.batches = zs, invstds, batches
-        ctx.means = [m if m is None or b else m.clone() for m, b in zip(means, batches)]
+        ctx.means = [None if m is None else saved_mean(m, b) for m, b in zip(means, batches)]
         ctx.save_for_backward(x, pre_img, pre_hm, w0, w1, w2, g0, g1, g2, b0, b1, b2)
         return y.buf
 
@@ -264,7 +219,7 @@ class _StemsFunction(torch.autograd.Function):
 def _stems(inputs, layers):
     """The stems on NCHW tensors -> the NHWC ``[N,H,W,16]`` tensor of their sum"""
     inputs = tuple(None if t is None else t.contiguous() for t in inputs)
-    if _recording():
+    if recording():
         # the parameters are read from the modules at every call: three weights, three gammas, three betas
         par = [None if m is None else p(m) for p in (lambda m: m[0].weight, lambda m: m[1].weight, lambda m: m[1].bias)
                for m in layers]
@@ -446,7 +401,7 @@ class DLA(nn.Module):
             parts.append((getattr(self, name), t) if t is not None else (None, None))
         for _, t in parts:
             if t is not None:
-                _need_cuda(t)
+                need_cuda(t, 'centertrack_amd backbone')
         return parts
 
     def _stems(self, x, pre_img, pre_hm):
@@ -466,7 +421,7 @@ class DLA(nn.Module):
             parts = self._stem_parts(x, pre_img, pre_hm)
             y = _stems([t for _, t in parts], [m for m, _ in parts])
         else:
-            with torch.set_grad_enabled(_recording()):
+            with torch.set_grad_enabled(recording()):
                 y = self._stems(x, pre_img, pre_hm)
             y = to_nhwc(y)
         return self._levels_nhwc(y)

@@ -20,19 +20,13 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib, dcn_v2, ops
+from . import _lib, _train, dcn_v2, ops
+from ._train import BN_MOMENTUM, bn_statistics, recording, saved_mean, to_nchw, update_running_stats  # noqa: F401
 from .ops import View
 
-BN_MOMENTUM = 0.1
 
-
-def _need_cuda(x, what):
-    if not x.is_cuda:
-        raise _lib.CTError('centertrack_amd %s runs on an MI355X only (got a %s tensor); no CPU fallback' % (what, x.device))
-    if x.dtype != torch.float32:
-        raise _lib.CTError('centertrack_amd %s computes in fp32 (got %s)' % (what, x.dtype))
-    if x.dim() != 4:
-        raise _lib.CTError('centertrack_amd %s wants a 4-d tensor (got %s)' % (what, tuple(x.shape)))
+def to_nhwc(x):
+    return _train.to_nhwc(x, 'neck')
 
 
 def fill_up_weights(up):
@@ -46,64 +40,7 @@ def fill_up_weights(up):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# layout at the public boundary
-
-class _ToNHWC(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        return ops.view_from_nchw(x).buf
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        return ops.view_to_nchw(View(g.contiguous()))
-
-
-class _ToNCHW(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        return ops.view_to_nchw(View(x))
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        return ops.view_from_nchw(g).buf
-
-
-def _recording():
-    return dcn_v2.is_trainable() and torch.is_grad_enabled()
-
-
-def to_nhwc(x):
-    """NCHW fp32 CUDA tensor -> contiguous ``[N,H,W,C]`` tensor (differentiable while a graph is recorded)"""
-    _need_cuda(x, 'neck')
-    if x.shape[1] % 4:
-        raise _lib.CTError('centertrack_amd neck needs channels %% 4 == 0 (got %d)' % x.shape[1])
-    if _recording():
-        return _ToNHWC.apply(x)
-    with torch.no_grad():
-        return ops.view_from_nchw(x).buf
-
-
-def to_nchw(x):
-    if _recording():
-        return _ToNCHW.apply(x)
-    with torch.no_grad():
-        return ops.view_to_nchw(View(x))
-
-
-# ---------------------------------------------------------------------------------------------------------------------
 # DeformConv
-
-@torch.no_grad()
-def update_running_stats(bn, mean, var, P):
-    """What a training-mode ``nn.BatchNorm2d`` does with the batch statistics of ``P`` values per channel: the counter, the
-    momentum (``None`` = cumulative average) and the unbiased variance"""
-    bn.num_batches_tracked += 1
-    m = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
-    bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
-    bn.running_var.mul_(1 - m).add_(var, alpha=m * P / (P - 1))
-
 
 def _deform_forward(x, mod):
     """``DeformConv.forward`` on the NHWC view ``x`` -> (output view, what a backward needs)"""
@@ -117,16 +54,7 @@ def _deform_forward(x, mod):
                     out=ops.new_view(x.N, x.H, x.W, 32, dev))
     om = View(om.buf, 0, 27)
     z = ops.dcn_v2(x, om, ops.pack_weight(dcn.weight.detach()), dcn.out_channels, shift=dcn.bias.detach())
-    batch = bn.training or bn.running_mean is None
-    if batch:
-        P = x.N * x.H * x.W
-        if P == 1:
-            raise _lib.CTError('DeformConv: training-mode BatchNorm needs more than one value per channel (N*H*W == 1)')
-        mean, var, invstd = ops.bn_stats(z, bn.eps)
-        if bn.training and bn.running_mean is not None:
-            update_running_stats(bn, mean, var, P)
-    else:
-        mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+    mean, invstd, batch = bn_statistics(bn, z, 'DeformConv')
     y = ops.bn_relu_apply(z, mean, invstd, bn.weight.detach(), bn.bias.detach())
     return y, (om, z, mean, invstd, batch)
 
@@ -138,7 +66,7 @@ class _DeformConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, w_off, b_off, gamma, beta, mod):
         y, (om, z, mean, invstd, batch) = _deform_forward(View(x), mod)
-        ctx.om, ctx.z, ctx.mean, ctx.invstd, ctx.batch = om, z, mean.clone() if not batch else mean, invstd, batch
+        ctx.om, ctx.z, ctx.mean, ctx.invstd, ctx.batch = om, z, saved_mean(mean, batch), invstd, batch
         ctx.save_for_backward(x, weight, w_off, gamma, beta)
         return y.buf
 
@@ -166,11 +94,8 @@ class _DeformConvFunction(torch.autograd.Function):
         if need_off:
             gwoff, gboff = ops.conv_backward_weight(xv, gom, 3, need_bias=need_boff)
         if need_x:
-            # gx += conv3x3(gom, w_off^T): w_offT[ci, co, ky, kx] = w_off[co, ci, 2 - ky, 2 - kx], co padded 27 -> 32 with zeros
-            wt = torch.zeros((xv.C, 32, 3, 3), dtype=torch.float32, device=x.device)
-            wt[:, :27] = w_off.detach().permute(1, 0, 2, 3).flip(2, 3)
-            gx = ops.conv2d(View(gom.buf, 0, 32), ops.pack_weight(wt), xv.C, 3, 1, res=gx,
-                            out=ops.new_view(xv.N, xv.H, xv.W, xv.C, x.device))
+            # gx += conv3x3(gom, w_off^T) over the 32-wide buffer
+            gx = ops.conv_backward_input(gom, w_off.detach(), res=gx, out=ops.new_view(xv.N, xv.H, xv.W, xv.C, x.device))
         return (gx.buf if need_x else None, gw if need_w else None, gb if need_b else None,
                 gwoff if need_woff else None, gboff if need_boff else None, ggamma, gbeta, None)
 
@@ -187,7 +112,7 @@ class DeformConv(nn.Module):
 
     def forward_nhwc(self, x):
         """``x``: contiguous ``[N,H,W,chi]`` fp32 CUDA tensor -> ``[N,H,W,cho]``"""
-        if _recording():
+        if recording():
             c, bn = self.conv, self.actf[0]
             return _DeformConvFunction.apply(x, c.weight, c.bias, c.conv_offset_mask.weight, c.conv_offset_mask.bias,
                                              bn.weight, bn.bias, self)
@@ -224,7 +149,7 @@ def _upsample_add(x, skip, up):
     f = up.stride[0]
     if tuple(skip.shape) != (x.shape[0], x.shape[1] * f, x.shape[2] * f, x.shape[3]):
         raise _lib.CTError('IDAUp: up x%d of %s does not fit the skip %s (NHWC)' % (f, tuple(x.shape), tuple(skip.shape)))
-    if _recording():
+    if recording():
         return _UpsampleAddFunction.apply(x, skip, up.weight, f)
     with torch.no_grad():
         return ops.upsample_add(View(x), up.weight.detach(), f, View(skip)).buf

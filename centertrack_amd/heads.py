@@ -17,6 +17,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
+from ._train import need_cuda
 
 
 def _one_head_conv(head_conv, heads):
@@ -33,16 +34,19 @@ def _one_head_conv(head_conv, heads):
     return hc
 
 
+def _split(names, params):
+    """``params`` = (w0, b0, w2, b2) per head in the order of ``names``, detached -> ([w0], [b0], {head: w2}, {head: b2})"""
+    p = [t.detach() for t in params]
+    return p[0::4], p[1::4], OrderedDict(zip(names, p[2::4])), OrderedDict(zip(names, p[3::4]))
+
+
 class _HeadsFunction(torch.autograd.Function):
     """(head names, feat, *(w0, b0, w2, b2 per head)) -> the heads' raw logits.  ``feat``: NCHW tensor or ``ops.View``."""
 
     @staticmethod
     def forward(ctx, names, feat, *params):
         nh = len(names)
-        p = [t.detach() for t in params]
-        w0s, b0s = p[0::4], p[1::4]
-        w2s = OrderedDict(zip(names, p[2::4]))
-        b2s = OrderedDict(zip(names, p[3::4]))
+        w0s, b0s, w2s, b2s = _split(names, params)
         grad = any(ctx.needs_input_grad)
         if isinstance(feat, ops.View):
             # what backward reads lives in storage private to this call: the caller's view is usually a buffer of a launch
@@ -68,12 +72,12 @@ def _heads_gradients(names, x, mid, params, need, gouts):
     """what both heads functions compute in backward -> (``ops.heads_backward``'s result, the parameter gradients in the order
     of ``params``); ``need`` = the function's ``needs_input_grad`` (names, feat, *params)"""
     nh = len(names)
-    p = [t.detach() for t in params]
-    hc = p[0].shape[0]
+    w0s, _, w2s, _ = _split(names, params)
+    hc = w0s[0].shape[0]
     needs = {'x': need[1], 'w0': any(need[2 + 4 * j] for j in range(nh)), 'b0': any(need[3 + 4 * j] for j in range(nh)),
              'w2': {h: need[4 + 4 * j] for j, h in enumerate(names)}, 'b2': {h: need[5 + 4 * j] for j, h in enumerate(names)}}
-    w0 = torch.cat(p[0::4], 0) if needs['x'] else None
-    res = ops.heads_backward(x, mid, dict(zip(names, gouts)), w0, OrderedDict(zip(names, p[2::4])), needs)
+    w0 = torch.cat(w0s, 0) if needs['x'] else None
+    res = ops.heads_backward(x, mid, dict(zip(names, gouts)), w0, w2s, needs)
     grads = []
     for j, h in enumerate(names):
         grads += [res['w0'][hc * j:hc * (j + 1)] if need[2 + 4 * j] else None,
@@ -88,9 +92,8 @@ class _HeadsNHWCFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, names, feat, *params):
-        p = [t.detach() for t in params]
-        outs, mid = ops.heads_forward_train(ops.View(feat.detach()), torch.cat(p[0::4], 0), torch.cat(p[1::4], 0),
-                                            OrderedDict(zip(names, p[2::4])), OrderedDict(zip(names, p[3::4])))
+        w0s, b0s, w2s, b2s = _split(names, params)
+        outs, mid = ops.heads_forward_train(ops.View(feat.detach()), torch.cat(w0s, 0), torch.cat(b0s, 0), w2s, b2s)
         if any(ctx.needs_input_grad):
             ctx.names, ctx.mid = names, mid
             ctx.save_for_backward(feat, *params)
@@ -142,23 +145,22 @@ class FusedHeads(nn.Module):
         fc = getattr(self, h)
         return fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias
 
-    def forward(self, feat):
-        if isinstance(feat, ops.View):
-            dev, cin = feat.buf.device, feat.C
-        elif torch.is_tensor(feat) and feat.dim() == 4:
-            dev, cin = feat.device, feat.shape[1]
-            if feat.dtype != torch.float32:
-                raise _lib.CTError('FusedHeads computes in fp32 (got %s)' % feat.dtype)
-        else:
-            raise _lib.CTError('FusedHeads takes an NCHW tensor or an ops.View')
-        if dev.type != 'cuda':
-            raise _lib.CTError('FusedHeads runs on an MI355X only (got a %s tensor); no CPU fallback' % dev)
+    def _check_input(self, t, cin):
+        """``t``: the 4-d tensor behind the input, ``cin``: the input's channel count"""
+        need_cuda(t, 'FusedHeads', dims=None)
         if cin != self.in_channels:
             raise _lib.CTError('FusedHeads was built for %d input channels (got %d)' % (self.in_channels, cin))
+
+    def forward(self, feat):
+        if isinstance(feat, ops.View):
+            self._check_input(feat.buf, feat.C)
+        elif torch.is_tensor(feat) and feat.dim() == 4:
+            self._check_input(feat, feat.shape[1])
+        else:
+            raise _lib.CTError('FusedHeads takes an NCHW tensor or an ops.View')
         params = [t for h in self.heads for t in self.head_parameters(h)]
         outs = _HeadsFunction.apply(tuple(self.heads), feat, *params)
         return OrderedDict(zip(self.heads, outs))
-
 
     def forward_nhwc(self, feat):
         """``feat``: an ``[N,H,W,in_channels]`` fp32 CUDA tensor (the layout of every trainable module's ``forward_nhwc``),
@@ -166,12 +168,7 @@ class FusedHeads(nn.Module):
         form of ``feat``; the input gradient is NHWC."""
         if not torch.is_tensor(feat) or feat.dim() != 4:
             raise _lib.CTError('FusedHeads.forward_nhwc takes an [N,H,W,C] tensor')
-        if feat.dtype != torch.float32:
-            raise _lib.CTError('FusedHeads computes in fp32 (got %s)' % feat.dtype)
-        if feat.device.type != 'cuda':
-            raise _lib.CTError('FusedHeads runs on an MI355X only (got a %s tensor); no CPU fallback' % feat.device)
-        if feat.shape[3] != self.in_channels:
-            raise _lib.CTError('FusedHeads was built for %d input channels (got %d)' % (self.in_channels, feat.shape[3]))
+        self._check_input(feat, feat.shape[3])
         params = [t for h in self.heads for t in self.head_parameters(h)]
         outs = _HeadsNHWCFunction.apply(tuple(self.heads), feat.contiguous(), *params)
         return OrderedDict(zip(self.heads, outs))

@@ -7,7 +7,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, _train          # (_train imports this module in turn: each reads the other at call time only)
 from ._lib import CT_OUT_NCHW, CT_RELU, ConvDesc, DcnBwdDesc, DcnDesc, DecodeDesc
 
 
@@ -57,28 +57,31 @@ def view_to_nchw(v):
     return out
 
 
-def pack_weight(w):
-    """OIHW conv weight (cuda, fp32) -> MFMA fragment layout (see centertrack_hip.h)."""
+def _pack(entry, elems, w, *dims, what=None):
+    """The OIHW weight ``w`` in the layout ``entry`` (a ``ct_pack_*``) writes: ``elems`` (its ``ct_packed_*_elems``) and
+    ``entry`` both take ``dims``.  ``what``: the refusal of a shape for which ``elems`` answers 0."""
     lib = _lib.load()
     w = w.contiguous().float()
+    n = getattr(lib, elems)(*dims)
+    if what is not None and not n:
+        raise _lib.CTError(what)
+    out = torch.empty(n, dtype=torch.float32, device=w.device)
+    _lib.check(getattr(lib, entry)(w.data_ptr(), out.data_ptr(), *dims, _lib.stream_ptr()), entry)
+    return out
+
+
+def pack_weight(w):
+    """OIHW conv weight (cuda, fp32) -> MFMA fragment layout (see centertrack_hip.h)."""
     Cout, Cin, ks, ks2 = w.shape
     assert ks == ks2 and Cin % 16 == 0, 'Cin must be a multiple of 16'
-    out = torch.empty(lib.ct_packed_weight_elems(Cout, Cin, ks), dtype=torch.float32, device=w.device)
-    _lib.check(lib.ct_pack_conv_weight(w.data_ptr(), out.data_ptr(), Cout, Cin, ks, _lib.stream_ptr()),
-               'ct_pack_conv_weight')
-    return out
+    return _pack('ct_pack_conv_weight', 'ct_packed_weight_elems', w, Cout, Cin, ks)
 
 
 def pack_winograd(w):
     """OIHW 3x3 conv weight -> Winograd F(2x2,3x3) fragments (ct_conv2d algo 201 / 202)"""
-    lib = _lib.load()
-    w = w.contiguous().float()
     Cout, Cin, ks, ks2 = w.shape
     assert ks == 3 and ks2 == 3 and Cin % 16 == 0
-    out = torch.empty(lib.ct_packed_winograd_elems(Cout, Cin), dtype=torch.float32, device=w.device)
-    _lib.check(lib.ct_pack_winograd_weight(w.data_ptr(), out.data_ptr(), Cout, Cin, _lib.stream_ptr()),
-               'ct_pack_winograd_weight')
-    return out
+    return _pack('ct_pack_winograd_weight', 'ct_packed_winograd_elems', w, Cout, Cin)
 
 
 def _p(t):
@@ -135,11 +138,7 @@ def conv2d(x, wp, Cout, ks, stride=1, out=None, **kw):
         out = new_view(x.N, Ho, Wo, Cout, x.buf.device, ld=(Cout + 3) // 4 * 4)
     d = make_conv_desc(x, wp, Cout, ks, stride, out=out, **kw)
     if d.workspace is None and kw.get('split_k', 0) != 1:
-        need = lib.ct_conv2d_workspace_bytes(ctypes.byref(d))
-        if need:
-            ws = torch.empty(need // 4, dtype=torch.float32, device=x.buf.device)
-            d.workspace, d.workspace_bytes = ws.data_ptr(), need
-            kw['_keep'] = ws
+        _ws = _workspace(lib, 'ct_conv2d_workspace_bytes', d, x.buf.device, optional=True)
     _lib.check(lib.ct_conv2d(ctypes.byref(d), _lib.stream_ptr()), 'ct_conv2d')
     return out if out is not None else kw['out_nchw']
 
@@ -187,25 +186,17 @@ def dcn_v2(x, om, wp, Cout, scale=None, shift=None, relu=False, out=None, split_
         part = torch.empty((x.C // 64) * x.N * x.H * x.W * 32, dtype=torch.float32, device=x.buf.device)
     d = make_dcn_desc(x, om, wp, Cout, scale, shift, relu, out, split_k=split_k, algo=algo, w_off=w_off, b_off=b_off,
                       up=up, om_partial=part, w_off_wino=w_off_wino if split_offsets else None)
-    ws = None
     if split_k != 1:
-        need = lib.ct_dcn_v2_workspace_bytes(ctypes.byref(d))
-        if need:
-            ws = torch.empty(need // 4, dtype=torch.float32, device=x.buf.device)
-            d.workspace, d.workspace_bytes = ws.data_ptr(), need
+        _ws = _workspace(lib, 'ct_dcn_v2_workspace_bytes', d, x.buf.device, optional=True)
     _lib.check(lib.ct_dcn_v2(ctypes.byref(d), _lib.stream_ptr()), 'ct_dcn_v2')
     return out
 
 
 def pack_weight_t(w):
     """OIHW 3x3 DCN weight -> the transposed fragment layout ct_dcn_v2_backward contracts gy with (centertrack_hip.h)."""
-    lib = _lib.load()
-    w = w.contiguous().float()
     Cout, Cin, ks, ks2 = w.shape
     assert ks == 3 and ks2 == 3 and Cin % 16 == 0
-    out = torch.empty(lib.ct_packed_dcn_weight_t_elems(Cout, Cin), dtype=torch.float32, device=w.device)
-    _lib.check(lib.ct_pack_dcn_weight_t(w.data_ptr(), out.data_ptr(), Cout, Cin, _lib.stream_ptr()), 'ct_pack_dcn_weight_t')
-    return out
+    return _pack('ct_pack_dcn_weight_t', 'ct_packed_dcn_weight_t_elems', w, Cout, Cin)
 
 
 def make_dcn_bwd_desc(x, om, gy, wT=None, gx=None, gom=None, gw=None, gb=None, workspace=None):
@@ -253,10 +244,7 @@ def dcn_v2_backward(x, om, gy, wT=None, need_x=True, need_om=True, need_w=True, 
     gw = torch.empty((gy.C, x.C, 3, 3), dtype=torch.float32, device=dev) if need_w or need_b else None
     gb = torch.empty(gy.C, dtype=torch.float32, device=dev) if need_b else None
     d = make_dcn_bwd_desc(x, om, gy, wT, gx, gom, gw, gb)
-    need = lib.ct_dcn_v2_backward_workspace_bytes(ctypes.byref(d))
-    if need:
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    _ws = _workspace(lib, 'ct_dcn_v2_backward_workspace_bytes', d, dev, optional=True)
     _lib.check(lib.ct_dcn_v2_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_dcn_v2_backward')
     return gx, gom, (gw if need_w else None), gb
 
@@ -295,11 +283,14 @@ def make_loss_desc(heads, grads=None):
     return d, arr
 
 
-def _workspace(lib, query_name, d, dev):
+def _workspace(lib, query_name, d, dev, optional=False):
     """Allocate what ``query_name`` (a ``ct_*_workspace_bytes``) asks for the descriptor ``d`` and hand it to ``d``; 0 bytes is
-    a rejected descriptor.  The caller keeps the returned tensor alive over its launch."""
+    a rejected descriptor or, with ``optional``, "none needed" (-> None).  The caller keeps the returned tensor alive over its
+    launch."""
     need = getattr(lib, query_name)(ctypes.byref(d))
     if not need:
+        if optional:
+            return None
         raise _lib.CTError('%s: %s' % (query_name, lib.ct_last_error().decode()))
     ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
     d.workspace, d.workspace_bytes = ws.data_ptr(), need
@@ -356,11 +347,28 @@ def conv_backward_weight(x, gy, ks, need_bias=True):
     return gw, gb
 
 
+def conv_backward_input(gy, w, res=None, out=None):
+    """Input gradient of ``conv(x, w)`` (OIHW ``w``, ``ks`` 1 or 3, stride 1, pad ks // 2) for the output gradient view ``gy``
+    (+ ``res``, into ``out`` if given), on the forward conv kernels: ``conv(gy, wt)`` with ``wt[ci, co, ky, kx] =
+    w[co, ci, ks - 1 - ky, ks - 1 - kx]``.  Those kernels contract multiples of 16 channels: where ``w.shape[0]`` is none (the
+    DeformConv's 27 offset/mask channels in a 32-wide buffer), ``gy`` must start its buffer, ``wt`` is zero-padded to ``gy.ld``
+    channels and the full width of ``gy.buf`` is contracted -- its pad channels must hold zeros."""
+    Cout, Cin, ks, _ = w.shape
+    wt = w.permute(1, 0, 2, 3).flip(2, 3)
+    if Cout % 16:
+        if gy.c0 or gy.ld % 16:
+            raise _lib.CTError('conv_backward_input: %d output channels need a view at the start of a buffer whose width is a '
+                               'multiple of 16 (got c0=%d, ld=%d)' % (Cout, gy.c0, gy.ld))
+        padded = torch.zeros((Cin, gy.ld, ks, ks), dtype=torch.float32, device=w.device)
+        padded[:, :Cout] = wt
+        wt, gy = padded, View(gy.buf, 0, gy.ld)
+    else:
+        wt = wt.contiguous()
+    return conv2d(gy, pack_weight(wt), Cin, ks, 1, res=res, out=out)
+
+
 def _head_tensor(t, what):
-    if not t.is_cuda:
-        raise _lib.CTError('%s runs on an MI355X only (got a %s tensor); no CPU fallback' % (what, t.device))
-    if t.dtype != torch.float32:
-        raise _lib.CTError('%s computes in fp32 (got %s)' % (what, t.dtype))
+    _train.need_cuda(t, what, dims=None)
     return t.detach().contiguous()
 
 
@@ -469,10 +477,7 @@ def heads_backward(feat, mid, gouts, w0, w2s, needs, gmid=None):
         gw0, gb0 = conv_backward_weight(feat, gmid, 3, need_bias=need_b0)
         res['w0'], res['b0'] = (gw0 if need_w0 else None), gb0
     if need_x:
-        # conv3x3(gmid, w0^T): w0T[ci, co, ky, kx] = w0[co, ci, 2 - ky, 2 - kx], on the forward conv kernels
-        w0 = _head_tensor(w0, 'heads_backward')
-        w0t = w0.permute(1, 0, 2, 3).flip(2, 3).contiguous()
-        res['x'] = conv2d(gmid, pack_weight(w0t), w0.shape[1], 3, 1)
+        res['x'] = conv_backward_input(gmid, _head_tensor(w0, 'heads_backward'))
     return res
 
 
@@ -619,16 +624,12 @@ def mask_sigmoid_backward(gom, om):
 
 def pack_weight_s2t(w):
     """OIHW 3x3 conv weight -> the fragment layout the stride-2 input gradient contracts gy with (centertrack_hip.h)."""
-    lib = _lib.load()
-    w = w.contiguous().float()
     Cout, Cin, ks, ks2 = w.shape
-    n = lib.ct_packed_conv_weight_s2t_elems(Cout, Cin)
-    if ks != 3 or ks2 != 3 or not n:
-        raise _lib.CTError('pack_weight_s2t: a [Cout,Cin,3,3] weight with Cout %% 16 == 0 and Cin %% 16 == 0 expected (got %s)'
-                           % (tuple(w.shape),))
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    _lib.check(lib.ct_pack_conv_weight_s2t(w.data_ptr(), out.data_ptr(), Cout, Cin, _lib.stream_ptr()), 'ct_pack_conv_weight_s2t')
-    return out
+    what = ('pack_weight_s2t: a [Cout,Cin,3,3] weight with Cout %% 16 == 0 and Cin %% 16 == 0 expected (got %s)'
+            % (tuple(w.shape),))
+    if ks != 3 or ks2 != 3:
+        raise _lib.CTError(what)
+    return _pack('ct_pack_conv_weight_s2t', 'ct_packed_conv_weight_s2t_elems', w, Cout, Cin, what=what)
 
 
 def conv_s2_backward(x, gy, w=None, need_x=True, need_w=True, gx=None):
@@ -968,20 +969,25 @@ class Decoder(object):
         return ret
 
 
+def _fill_targets_desc(t, staging_host, staging_dev, words, B, max_objs, slot_words, nout, pre_hm):
+    """the fields of a ``ct_targets_desc`` that ``build_targets`` and ``build_pose_targets`` fill alike"""
+    t.staging_host, t.staging_dev, t.words = staging_host.data_ptr(), staging_dev.data_ptr(), words
+    t.B, t.max_objs, t.slot_words, t.nout = B, max_objs, slot_words, nout
+    if pre_hm is not None:
+        t.pre_hm = pre_hm.data_ptr()
+        t.H, t.W = pre_hm.shape[2:]
+
+
 def build_targets(staging_host, staging_dev, words, B, max_objs, slot_words, nout, hm=None, pre_hm=None):
     """ct_build_targets (csrc/targets.hip) on the current stream: upload ``words`` int32 words of the packed batch from the
     pinned ``staging_host`` to ``staging_dev`` and write hm [B,C,h,w], pre_hm [B,1,H,W] (either may be None) and the slot
     tensors the buffer's output table names, in one launch.  ``centertrack_amd.targets.TargetBuilder.render`` packs the
     buffer; bad contents raise ``CTError`` before anything is enqueued."""
     d = _lib.TargetsDesc()
-    d.staging_host, d.staging_dev, d.words = staging_host.data_ptr(), staging_dev.data_ptr(), words
-    d.B, d.max_objs, d.slot_words, d.nout = B, max_objs, slot_words, nout
+    _fill_targets_desc(d, staging_host, staging_dev, words, B, max_objs, slot_words, nout, pre_hm)
     if hm is not None:
         d.hm = hm.data_ptr()
         _, d.C, d.h, d.w = hm.shape
-    if pre_hm is not None:
-        d.pre_hm = pre_hm.data_ptr()
-        d.H, d.W = pre_hm.shape[2:]
     _lib.check(_lib.load().ct_build_targets(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_targets')
 
 
@@ -993,16 +999,12 @@ def build_pose_targets(staging_host, staging_dev, words, B, max_objs, slot_words
     the buffer; bad contents raise ``CTError`` before anything is enqueued."""
     d = _lib.PoseTargetsDesc()
     t = d.base
-    t.staging_host, t.staging_dev, t.words = staging_host.data_ptr(), staging_dev.data_ptr(), words
-    t.B, t.max_objs, t.slot_words, t.nout = B, max_objs, slot_words, nout
+    _fill_targets_desc(t, staging_host, staging_dev, words, B, max_objs, slot_words, nout, pre_hm)
     t.C, (t.h, t.w), d.J = C, hw, J
     if hm is not None:
         t.hm = hm.data_ptr()
     if hm_hp is not None:
         d.hm_hp = hm_hp.data_ptr()
-    if pre_hm is not None:
-        t.pre_hm = pre_hm.data_ptr()
-        t.H, t.W = pre_hm.shape[2:]
     _lib.check(_lib.load().ct_build_pose_targets(ctypes.byref(d), _lib.stream_ptr()), 'ct_build_pose_targets')
 
 
