@@ -1059,6 +1059,8 @@ extern "C" int ct_decode(const ct_decode_desc *d, void *stream)
         return CT_ERR_WORKSPACE;
     }
     if (d->w > 4096) CT_FAIL_ARG("ct_decode: w=%d > 4096 unsupported", d->w);
+    // (every argument error returns before the first launch: a refused call leaves nothing enqueued)
+    if (d->out_stride && d->out_stride < ct_decode_row_floats(d)) CT_FAIL_ARG("ct_decode: out_stride %d < row floats", d->out_stride);
     hipStream_t s = (hipStream_t)stream;
     Stage1Args a1;
     a1.hm = d->hm; a1.cand = (unsigned long long *)d->workspace;
@@ -1086,7 +1088,6 @@ extern "C" int ct_decode(const ct_decode_desc *d, void *stream)
     a2.out = d->out; a2.inds = (long long *)d->inds;
     a2.B = d->B; a2.C = d->C; a2.h = d->h; a2.w = d->w; a2.K = d->K; a2.nseg = nseg;
     a2.F = d->out_stride ? d->out_stride : ct_decode_row_floats(d);   // floats between consecutive rows
-    if (a2.F < ct_decode_row_floats(d)) CT_FAIL_ARG("ct_decode: out_stride %d < row floats", d->out_stride);
     a2.M2 = (int)M2; a2.keys_final = 0;
     a2.host_out = d->host_out; a2.done_flag = d->done_flag; a2.done_counter = d->done_counter;
     a2.present = present_mask(d);

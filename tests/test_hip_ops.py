@@ -915,10 +915,14 @@ def test_decode_pose_rejects_what_it_does_not_implement(device):
     ('cluster_coco', 20, 128, 128, 2, 100, 'cluster'),  # ... and the radix-select fallback of stage 2a
 ])
 def test_decode_selection_paths_full_size(device, name, C, h, w, B, K, dense):
-    """every selection path of stage 2 / 2a (round 3: candidates in registers, linear score histogram, ranked boundary
+    """full-size maps through stage 2a and stage 2 (round 3: candidates in registers, linear score histogram, ranked boundary
     bin; fallbacks for clustered scores) against the oracle's generic_decode: indices, classes, scores and boxes
     bit-exact.  Scores are DISTINCT by construction (a permutation of an arithmetic sequence): exact float32 ties among
-    the top K would be ordered arbitrarily by torch.topk."""
+    the top K would be ordered arbitrarily by torch.topk.
+    In the label table of tests/_decode_paths.py the six random / dense cases all end in regs:hist (behind 2a:hist where
+    there is a stage 2a; the last slice of dense_k512 is a 2a:few); cluster_mot owns regs:bitonic and cluster_coco owns
+    2a:radix.  The other ends of stage 2 (regs:rank, regs:radix, regs:slow, mem:bitonic, mem:rank, mem:radix, mem:slow)
+    and the tied cuts are reached by tests/test_hip_decode_paths.py, not here."""
     from collections import OrderedDict
     from centertrack_amd import ops
     from oracle import decode as odecode
