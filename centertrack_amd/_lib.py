@@ -326,6 +326,13 @@ class OptimRec(ctypes.Structure):
                 ('reserved', ctypes.c_int * 13)]
 
 
+class SlotDesc(ctypes.Structure):
+    _fields_ = [('map', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('C', ctypes.c_int), ('ld', ctypes.c_int),
+                ('ind', ctypes.c_void_p), ('M', ctypes.c_int),
+                ('rows', ctypes.c_void_p), ('ldr', ctypes.c_int)]
+
+
 ABI_VERSION = 103       # CT_ABI_VERSION of include/centertrack_hip.h
 
 EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_elems', 'ct_pack_conv_weight',
@@ -351,7 +358,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
            'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials',
-           'ct_optim_step']
+           'ct_optim_step', 'ct_slot_gather', 'ct_slot_fold']
 
 _lib = None
 
@@ -509,6 +516,8 @@ def load():
     lib.ct_build_inputs_partials.argtypes = [i, i]
     lib.ct_build_inputs.argtypes = [ctypes.POINTER(InputsDesc), p]
     lib.ct_optim_step.argtypes = [p, i, ctypes.c_longlong, i, p]
+    lib.ct_slot_gather.argtypes = [ctypes.POINTER(SlotDesc), p]
+    lib.ct_slot_fold.argtypes = [ctypes.POINTER(SlotDesc), p]
     # CENTERTRACK_TUNE="key=value,key=value": launch-heuristic knobs of ct_set_tuning (A/B runs)
     for kv in filter(None, os.environ.get('CENTERTRACK_TUNE', '').split(',')):
         k, _, v = kv.partition('=')

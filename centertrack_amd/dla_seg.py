@@ -14,6 +14,10 @@ Covered: ``num_layers == 34``, ``opt.dla_node == 'dcn'``, ``opt.head_kernel == 3
 else raises ``CTError``.  Nothing is downloaded: the base is always built with ``pretrained=False``, whatever
 ``opt.load_model`` says (the reference downloads the ImageNet weights when it is ``''``); load them from a local file with
 ``model.base.load_pretrained_model`` or ``load_state_dict``.  CUDA fp32 tensors only: there is no CPU fallback.
+
+Slot heads (``opt.slot_heads``, ``heads.FusedHeads``): the CALL takes ``batch['ind']`` as a fourth argument, ``model(x, pre_img,
+pre_hm, ind)``, and then returns the heads of ``heads.SLOT_HEADS`` at the slots, ``[B, M, c]``.  ``forward`` itself keeps the
+reference's three parameters.
 """
 import numpy as np
 
@@ -26,7 +30,9 @@ DLA_NODE = {'dcn': (DeformConv, DeformConv)}
 
 class DLASeg(FusedHeads):
     """Reference ``DLASeg(num_layers, heads, head_convs, opt)``.  ``opt`` is read for ``dla_node``, ``head_kernel``,
-    ``prior_bias``, ``model_output_list``, ``pre_img`` and ``pre_hm``."""
+    ``prior_bias``, ``model_output_list``, ``pre_img``, ``pre_hm`` and ``slot_heads`` (default False: with it, ``model(x, pre_img,
+    pre_hm, ind)`` with ``ind`` = ``batch['ind']`` returns the heads of ``heads.SLOT_HEADS`` at the slots, ``[B, M, c]``;
+    ``FusedHeads``)."""
 
     def __init__(self, num_layers, heads, head_convs, opt):
         if num_layers != 34:
@@ -36,8 +42,10 @@ class DLASeg(FusedHeads):
             raise _lib.CTError('centertrack_amd DLASeg supports dla_node dcn only (got %r)' % (node,))
         if getattr(opt, 'head_kernel', 3) != 3:
             raise _lib.CTError('centertrack_amd DLASeg supports head_kernel 3 only (got %r)' % (opt.head_kernel,))
-        super().__init__(heads, head_convs, 64, prior_bias=getattr(opt, 'prior_bias', -4.6))
+        super().__init__(heads, head_convs, 64, prior_bias=getattr(opt, 'prior_bias', -4.6),
+                         slot_heads=bool(getattr(opt, 'slot_heads', False)))
         self.num_stacks = 1
+        self._slot_ind = None
         self.opt = opt
         self.node_type = DLA_NODE[node]
         down_ratio = 4
@@ -66,8 +74,18 @@ class DLASeg(FusedHeads):
     def imgpre2feats(self, x, pre_img=None, pre_hm=None):
         return [dla_base.to_nchw(self.feats_nhwc(x, pre_img, pre_hm))]
 
+    def __call__(self, x, pre_img=None, pre_hm=None, ind=None):
+        """the reference's call with ``batch['ind']`` as an optional fourth argument (slot heads).  ``forward`` has the
+        reference's signature, so ``ind`` reaches it through the instance, for the length of this call; hooks run as usual."""
+        self._slot_ind = ind
+        try:
+            return super().__call__(x, pre_img, pre_hm)
+        finally:
+            self._slot_ind = None
+
     def forward(self, x, pre_img=None, pre_hm=None):
-        z = self.forward_nhwc(self.feats_nhwc(x, pre_img, pre_hm))
+        feat = self.feats_nhwc(x, pre_img, pre_hm)
+        z = self.forward_nhwc(feat) if self._slot_ind is None else self.forward_nhwc(feat, self._slot_ind)
         if getattr(self.opt, 'model_output_list', False):
             return [[z[head] for head in sorted(self.heads)]]
         return [dict(z)]

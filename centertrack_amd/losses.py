@@ -16,6 +16,10 @@ Differences from the reference, all deliberate:
 * A slot whose ``ind`` is outside ``[0, H*W)`` or whose ``cat`` is outside ``[0, C)`` makes the reference raise (an index
   error, i.e. a host synchronisation).  Here it counts as a slot with mask 0 (``rot``: mask 0 and rotbin 0): it reads and
   writes nothing.
+* A 3-d entry ``[B,M,c]`` of ``outputs[s]`` is a slot head (``heads.FusedHeads`` with ``slot_heads``: the head evaluated at
+  ``batch['ind']`` only).  The slot heads of a stack are a second group of the same kernels, presented as maps ``[B,c,1,M]``
+  in which slot m reads cell m; an ``ind`` outside ``[0, H*W)`` of the stack's dense ``hm`` becomes the index -1, so the rule
+  above holds in both modes.  A stack with slot heads and no dense ``hm`` raises ``CTError``.
 
 CUDA tensors only: a CPU tensor raises ``CTError``.
 """
@@ -112,6 +116,31 @@ class GenericLoss(nn.Module):
         kind = CT_LOSS_L1_DEPTH if head == 'dep' else CT_LOSS_BCE if head == 'nuscenes_att' else CT_LOSS_L1
         return head_spec(kind, x, batch[head], batch[head + '_mask'], ind, None, head)
 
+    @staticmethod
+    def _slot_view(group, output, batch):
+        """The slot heads ``group`` of a stack as the kernels read them -> (outputs, batch): each ``[B,M,c]`` output is the map
+        ``[B,c,1,M]`` (the layout ``FusedHeads`` wrote it in: no copy) and slot m reads cell m of it.  A slot whose ``ind`` is
+        outside ``[0, H*W)`` of the stack's dense ``hm`` gets the index -1, which the kernels count as mask 0 (``rot``: and
+        rotbin 0): it reads and writes nothing, as in dense mode."""
+        dense_only = [h for h in group if h in ('hm', 'hm_hp', 'hp_offset')]
+        if dense_only:
+            raise _lib.CTError('GenericLoss: %s cannot be slot heads: they are not read at batch[\'ind\']' % (dense_only,))
+        hm = output.get('hm')
+        if not torch.is_tensor(hm) or hm.dim() != 4:
+            raise _lib.CTError('GenericLoss: slot heads %s without a dense hm map in the stack: the range of ind is unknown'
+                               % (group,))
+        ind = _i64(batch['ind'], 'ind').view(hm.shape[0], -1)
+        M = ind.shape[1]
+        valid = (ind >= 0) & (ind < hm.shape[2] * hm.shape[3])
+        proxy = torch.where(valid, torch.arange(M, device=ind.device).expand_as(ind), torch.full_like(ind, -1))
+        maps = {}
+        for h in group:
+            x = _cuda(output[h], h)
+            if x.shape[:2] != ind.shape:
+                raise _lib.CTError('GenericLoss: slot head %s is %s for ind %s' % (h, tuple(x.shape), tuple(ind.shape)))
+            maps[h] = x.transpose(1, 2).unsqueeze(2)
+        return maps, dict(batch, ind=proxy)
+
     def forward(self, outputs, batch):
         opt = self.opt
         losses = {head: 0 for head in opt.heads}
@@ -121,9 +150,13 @@ class GenericLoss(nn.Module):
             # and a head of opt.heads it has no loss for stays 0 in loss_stats and in tot)
             names = [h for h in opt.heads
                      if h in KNOWN_HEADS and h in output and (h != 'hp_offset' or 'hm_hp' in output)]
-            if names:
-                vec = fused_losses([self._spec(h, output, batch) for h in names])
-                for i, h in enumerate(names):
+            # a 3-d entry [B,M,c] is a slot head (heads.FusedHeads with slot_heads): the stack's second group
+            for group in ([h for h in names if output[h].dim() != 3], [h for h in names if output[h].dim() == 3]):
+                if not group:
+                    continue
+                src = (output, batch) if output[group[0]].dim() != 3 else self._slot_view(group, output, batch)
+                vec = fused_losses([self._spec(h, *src) for h in group])
+                for i, h in enumerate(group):
                     losses[h] = losses[h] + vec[i] / opt.num_stacks
             if self.sigmoid_outputs:
                 with torch.no_grad():

@@ -347,12 +347,14 @@ def conv_backward_weight(x, gy, ks, need_bias=True):
     return gw, gb
 
 
-def conv_backward_input(gy, w, res=None, out=None):
+def conv_backward_input(gy, w, res=None, out=None, ks=None):
     """Input gradient of ``conv(x, w)`` (OIHW ``w``, ``ks`` 1 or 3, stride 1, pad ks // 2) for the output gradient view ``gy``
     (+ ``res``, into ``out`` if given), on the forward conv kernels: ``conv(gy, wt)`` with ``wt[ci, co, ky, kx] =
-    w[co, ci, ks - 1 - ky, ks - 1 - kx]``.  Those kernels contract multiples of 16 channels: where ``w.shape[0]`` is none (the
+    w[co, ci, ks - 1 - ky, ks - 1 - kx]``.  ``ks``: what the caller expects ``w`` to be (None: whatever it is).  Those kernels contract multiples of 16 channels: where ``w.shape[0]`` is none (the
     DeformConv's 27 offset/mask channels in a 32-wide buffer), ``gy`` must start its buffer, ``wt`` is zero-padded to ``gy.ld``
     channels and the full width of ``gy.buf`` is contracted -- its pad channels must hold zeros."""
+    if ks is not None and tuple(w.shape[2:]) != (ks, ks):
+        raise _lib.CTError('conv_backward_input: a %dx%d weight where ks=%d was asked for' % (w.shape[2], w.shape[3], ks))
     Cout, Cin, ks, _ = w.shape
     wt = w.permute(1, 0, 2, 3).flip(2, 3)
     if Cout % 16:
@@ -372,22 +374,24 @@ def _head_tensor(t, what):
     return t.detach().contiguous()
 
 
-def heads_forward_train(feat, w0, b0, w2s, b2s):
+def heads_forward_train(feat, w0, b0, w2s, b2s, ks=3):
     """The heads (base_model.py:24-65) with the hidden map kept for a backward: ``feat`` NHWC view [N,H,W,Cin]; ``w0``
     [nheads*hc, Cin, 3, 3] / ``b0`` [nheads*hc] = the heads' first layers concatenated in the order of ``w2s``; ``w2s`` /
     ``b2s`` = {head: [c, hc(, 1, 1)]} / {head: [c]}.  -> (OrderedDict {head: raw logits NCHW [N,c,H,W]}, ``mid`` = the NHWC
     view [N,H,W,nheads*hc] after the ReLU).  The un-fused heads plan of the model: one ct_conv2d into ``mid``, one per
-    head into its logits; the weights are packed here, from what their storage holds now."""
+    head into its logits; the weights are packed here, from what their storage holds now.
+    ``ks`` = 1: the first layer is a 1x1 convolution, ``w0`` [nheads*hc, Cin, 1, 1] -- the heads at the slots, where ``feat``
+    is the gathered map [N,1,M,9*Cin'] of ``slot_gather``."""
     from collections import OrderedDict
     nh = len(w2s)
     w0, b0 = _head_tensor(w0, 'heads_forward_train'), _head_tensor(b0, 'heads_forward_train')
-    if nh == 0 or w0.shape[0] % nh or w0.shape[1] != feat.C or tuple(w0.shape[2:]) != (3, 3) or b0.numel() != w0.shape[0]:
+    if nh == 0 or w0.shape[0] % nh or w0.shape[1] != feat.C or tuple(w0.shape[2:]) != (ks, ks) or b0.numel() != w0.shape[0]:
         raise _lib.CTError('heads_forward_train: w0 %s / b0 %s do not fit %d heads on %d channels'
                            % (tuple(w0.shape), tuple(b0.shape), nh, feat.C))
     hc = w0.shape[0] // nh
     dev = feat.buf.device
     mid = new_view(feat.N, feat.H, feat.W, hc * nh, dev)
-    conv2d(feat, pack_weight(w0), hc * nh, 3, 1, shift=b0, relu=True, out=mid)
+    conv2d(feat, pack_weight(w0), hc * nh, ks, 1, shift=b0, relu=True, out=mid)
     out = OrderedDict()
     for j, (h, w2) in enumerate(w2s.items()):
         w2, b2 = _head_tensor(w2, 'heads_forward_train'), _head_tensor(b2s[h], 'heads_forward_train')
@@ -427,13 +431,14 @@ def make_heads_tail_desc(mid, gouts, w2s=None, gmid=None, gw2s=None, gb2s=None):
     return d, arr
 
 
-def heads_backward(feat, mid, gouts, w0, w2s, needs, gmid=None):
+def heads_backward(feat, mid, gouts, w0, w2s, needs, gmid=None, ks=3):
     """Gradients of ``heads_forward_train`` for the logit gradients ``gouts`` = {head: [N,c,H,W]} (every head, in the order
     of ``w2s``).  ``needs`` = {'x', 'w0', 'b0': bool, 'w2', 'b2': bool or {head: bool}}; missing keys are False.  Returns
     {'x': view or None, 'w0': [nheads*hc,Cin,3,3] or None, 'b0', 'w2': {head: [c,hc,1,1] or None}, 'b2': {head: ...},
     'gmid': the hidden gradient's view or None}: no buffer is allocated and no kernel runs for what was not asked for.
     ``gmid``: a caller-owned view for the hidden gradient (any pitch).  ``feat`` may be None when neither 'w0' nor 'b0' is
-    needed.  Every result is bitwise reproducible."""
+    needed.  Every result is bitwise reproducible.  ``ks``: the first layer's kernel size (``heads_forward_train``); 'w0' is
+    [nheads*hc,Cin,ks,ks]."""
     lib = _lib.load()
     heads = list(w2s)
     nh = len(heads)
@@ -474,11 +479,47 @@ def heads_backward(feat, mid, gouts, w0, w2s, needs, gmid=None):
         _lib.check(lib.ct_heads_tail_backward(ctypes.byref(d), _lib.stream_ptr()), 'ct_heads_tail_backward')
     res['w2'], res['b2'], res['gmid'] = dict(zip(heads, gw2)), dict(zip(heads, gb2)), gmid
     if need_w0 or need_b0:
-        gw0, gb0 = conv_backward_weight(feat, gmid, 3, need_bias=need_b0)
+        gw0, gb0 = conv_backward_weight(feat, gmid, ks, need_bias=need_b0)
         res['w0'], res['b0'] = (gw0 if need_w0 else None), gb0
     if need_x:
-        res['x'] = conv_backward_input(gmid, _head_tensor(w0, 'heads_backward'))
+        res['x'] = conv_backward_input(gmid, _head_tensor(w0, 'heads_backward'), ks=ks)
     return res
+
+
+def _slot_desc(what, view, ind, rows):
+    """``ct_slot_desc`` of the NHWC view ``view``, ``ind`` int64 [N,M] and the view ``rows`` [N,1,M,9*C]"""
+    if not torch.is_tensor(ind) or not ind.is_cuda:
+        raise _lib.CTError('%s runs on an MI355X only (ind is not a CUDA tensor); no CPU fallback' % what)
+    if ind.dtype != torch.int64 or ind.dim() != 2 or ind.shape[0] != view.N or not ind.is_contiguous():
+        raise _lib.CTError('%s: ind must be a contiguous int64 [%d, M] tensor (got %s %s)' % (what, view.N, ind.dtype, tuple(ind.shape)))
+    M = ind.shape[1]
+    if (rows.N, rows.H, rows.W, rows.C) != (view.N, 1, M, 9 * view.C):
+        raise _lib.CTError('%s: the rows are %s for %d slots of %d channels' % (what, (rows.N, rows.H, rows.W, rows.C), M, view.C))
+    d = _lib.SlotDesc()
+    d.map, d.N, d.H, d.W, d.C, d.ld = view.ptr, view.N, view.H, view.W, view.C, view.ld
+    d.ind, d.M = ind.data_ptr(), M
+    d.rows, d.ldr = rows.ptr, rows.ld
+    return d
+
+
+def slot_gather(feat, ind, out=None):
+    """The im2col rows of a 3x3, pad 1 convolution over the NHWC view ``feat`` at the cells ``ind`` (int64 [N,M], y * W + x) ->
+    the view [N,1,M,9*C], ``[n,0,m,(ky*3+kx)*C + c] = feat[n, y+ky-1, x+kx-1, c]``; 0 outside the map, a row of zeros for an
+    ``ind`` outside [0, H*W).  One launch, exact."""
+    if out is None and torch.is_tensor(ind) and ind.dim() == 2:
+        out = new_view(feat.N, 1, ind.shape[1], 9 * feat.C, feat.buf.device)
+    d = _slot_desc('slot_gather', feat, ind, out)
+    _lib.check(_lib.load().ct_slot_gather(ctypes.byref(d), _lib.stream_ptr()), 'ct_slot_gather')
+    return out
+
+
+def slot_fold(patches, ind, gx):
+    """The transpose of ``slot_gather``: adds the view ``patches`` [N,1,M,9*C] into the NHWC view ``gx`` in place (and returns
+    it).  No atomics: a cell is written once, by its lowest valid covering slot, as gx + (the covering slots' values added in
+    ascending slot order) -- bitwise reproducible; cells no slot covers are not written."""
+    d = _slot_desc('slot_fold', gx, ind, patches)
+    _lib.check(_lib.load().ct_slot_fold(ctypes.byref(d), _lib.stream_ptr()), 'ct_slot_fold')
+    return gx
 
 
 def stem(x, pre_img, pre_hm, w_x, w_img, w_hm, scale3, shift3, out=None):

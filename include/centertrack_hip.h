@@ -356,6 +356,30 @@ typedef struct ct_heads_tail_bwd_desc {
 int ct_heads_tail_backward(const ct_heads_tail_bwd_desc *d, void *stream);
 size_t ct_heads_tail_backward_workspace_bytes(const ct_heads_tail_bwd_desc *d);
 
+/* ---- the heads at the object slots (training with slot heads); additions under ABI 103.  A head the loss
+ * reads at batch['ind'] only is evaluated at those M cells per image: the im2col rows of the 3x3, pad 1 first layer are
+ * gathered into a map [N,1,M,9*C] on which the head is two 1x1 convolutions -- ct_conv2d, ct_heads_tail_backward and
+ * ct_conv2d_backward_weight with ks = 1 do all the arithmetic -- and the input gradient's patches are folded back.
+ *   map:  NHWC view [N,H,W,C] at pitch ld (C % 4 == 0, ld % 4 == 0, 16-byte aligned)
+ *   ind:  int64 [N,M], the cell y * W + x of a slot; a value outside [0, H*W) is an invalid slot
+ *   rows: [N*M] rows of 9*C floats at pitch ldr (ldr % 4 == 0, 16-byte aligned), rows[n,m,ky*3+kx,c]
+ * ct_slot_gather writes rows[n,m,tap,c] = map[n, y+ky-1, x+kx-1, c], 0 for a tap outside the map and a whole row of 0 for an
+ * invalid slot; it writes nothing beyond the 9*C floats of a row.  A copy: exact.
+ * ct_slot_fold adds rows into map, map[n, y+ky-1, x+kx-1, c] += rows[n,m,tap,c], without atomics.  Every touched cell has one
+ * owner, the lowest valid slot whose 3x3 neighbourhood covers it; the owner takes the patch value of that slot, adds those of
+ * the further covering slots in ascending slot order and stores map + sum once.  The float32 value of every cell is therefore
+ * defined exactly and equal from run to run; duplicates (up to all M slots on one cell) are summed, invalid slots contribute
+ * nothing, a cell no slot covers is not written.
+ * Both return CT_ERR_ARG before any launch for a null descriptor or pointer, a non-positive shape, M outside [1, 8192], a pitch
+ * below the channel count, a misaligned view, or a view of 2 GiB or more (N*H*W*ld*4, N*M*ldr*4). */
+typedef struct ct_slot_desc {
+    float *map; int N, H, W, C, ld;             /* read by ct_slot_gather, updated by ct_slot_fold */
+    const long long *ind; int M;
+    float *rows; int ldr;                       /* written by ct_slot_gather, read by ct_slot_fold */
+} ct_slot_desc;
+int ct_slot_gather(const ct_slot_desc *d, void *stream);
+int ct_slot_fold(const ct_slot_desc *d, void *stream);
+
 /* ---- the trainable neck (DeformConv / IDAUp / DLAUp, dla.py:506-574); additions under ABI 103.  All fp32 on NHWC views with
  * a channel pitch (ld >= C, C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers, channel slices allowed).  No atomics: every sum
  * runs thread -> workgroup -> slab in a fixed order, slab counts depend on the shapes only, every result is bitwise equal from
@@ -831,7 +855,7 @@ int ct_preprocess_lut(const float *mean, const float *stdv, int channels, float 
 int ct_preprocess_device(const uint8_t *img, int h, int w, int stride, int channels, const double *trans,
                          int dst_w, int dst_h, const float *lut, float *out, float *out_flip, void *stream);
 
-/* ---- training targets on the device (DESIGN.md section 16) -------------------------------------------------
+/* ---- training targets on the device (DESIGN.md section 22) -------------------------------------------------
  * Replaces, for a whole batch, the dense part of the reference's GenericDataset.__getitem__
  * (src/lib/dataset/generic_dataset.py:205-255 _get_pre_dets, :330-370 _init_ret, :386-398 _mask_ignore_or_crowd,
  * :423-515 _add_instance; draw_umich_gaussian, src/lib/utils/image.py:139-154) plus default_collate and
