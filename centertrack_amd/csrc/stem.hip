@@ -72,7 +72,11 @@ __global__ __launch_bounds__(256) void stem_kernel(StemArgs a)
         const int s = (k >= 296) ? 2 : ((k >= 148) ? 1 : 0);
         const int kk = k - st_koff(s);
         const int cin = (s == 2) ? 1 : 3;
-        int off = 0;
+        // a padding k (147 of stems 0 and 1, 49..51 of stem 2) carries a zero weight, but its A operand is still read: it
+        // must come from a plane THIS launch staged -- the stem's own first plane, finite whenever the input is.  Plane 0 is
+        // staged only when a.in[0] is given; in a {pre_img} / {pre_hm} launch it is whatever the previous kernel left in
+        // LDS, and NaN * 0 = NaN.
+        int off = (3 * s) * ST_PS;
         if (kk < cin * 49) {
             const int c = kk / 49, r = kk - c * 49;
             off = (3 * s + c) * ST_PS + (r / 7) * ST_PW + (r % 7);
