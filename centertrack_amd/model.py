@@ -11,16 +11,16 @@ libcentertrack_hip kernels on the current stream (capturable in one HIP graph).
 """
 import ctypes
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
-from . import _lib, autotune, ops
+from . import _lib, autotune, dcn_schedule, ops
+from .dcn_schedule import SMALL_SLOT_WGS  # noqa: F401  (its home; kept importable from here)
 from .ops import View
 from .weights import CHANNELS, LEVELS, dla34_param_shapes
 
 BN_EPS = 1e-5
-SMALL_SLOT_WGS = 600      # a MAIN slot with fewer workgroups than this (of 768 resident ones) may split K finer
 FUSE_OFFSET = os.environ.get('CENTERTRACK_FUSE_OFFSET', '1') != '0'
 WINOGRAD = os.environ.get('CENTERTRACK_WINOGRAD', '1') != '0'
 FUSE_HEADS = os.environ.get('CENTERTRACK_FUSE_HEADS', '1') != '0'
@@ -44,13 +44,9 @@ class _Launch(object):
         self.us, self.ws_need = us, ws_need
 
 
-class _DcnLayer(object):
-    """One DeformConv node of the IDAUp tree (dla.py:506-518) waiting to be scheduled: input view, output view, the
-    fused IDAUp step ``up`` = (weight, f, skip view, output view) of a `proj` node."""
-    __slots__ = ('name', 'x', 'cout', 'out', 'up', 'main', 'finish', 'desc', 'fused', 'splits', 'use_ws', 'nkk')
-
-    def __init__(self, name, x, cout, out, up):
-        self.name, self.x, self.cout, self.out, self.up = name, x, cout, out, up
+# The views of one DeformConv node of the IDAUp tree (dla.py:506-518): input view, output view, the fused IDAUp step
+# ``up`` = (weight, f, skip view, output view) of a `proj` node.  What the schedule makes of it is in dcn_schedule.Planned.
+_DcnLayer = namedtuple('_DcnLayer', 'name x cout out up')
 
 
 class DLASegHIP(torch.nn.Module):
@@ -327,13 +323,16 @@ class DLASegHIP(torch.nn.Module):
             feats.append(out)
             x = out
 
-        dcn_layers = []
+        dcn_layers, dcn_views = [], {}
 
         def deform(name, x, cout, out, up=None):
             """DeformConv.forward (dla.py:515-518): offset/mask conv -> DCNv2 -> BN -> ReLU; with ``up`` =
             (weight, f, skip view, output view) also the IDAUp step `up(.) + skip` (dla.py:543-545) that consumes a
-            `proj` node.  Only recorded here: the 16 nodes are scheduled together below (_schedule_dcn)."""
-            dcn_layers.append(_DcnLayer(name, x, cout, out, up))
+            `proj` node.  Only recorded here, buffers as keys: the 16 nodes are scheduled together (dcn_schedule.plan)
+            and materialised below (_schedule_dcn)."""
+            dcn_layers.append(dcn_schedule.Layer(name, id(x.buf), x.C, x.H, x.W, cout, id(out.buf),
+                                                 None if up is None else (up[1], id(up[2].buf), id(up[3].buf))))
+            dcn_views[name] = _DcnLayer(name, x, cout, out, up)
             return out
 
         def ida(p, layers, startp, endp, o, up_f):
@@ -356,10 +355,9 @@ class DLASegHIP(torch.nn.Module):
         ida('ida_up', y, 0, 3, 64, [1, 2, 4])
         feat = y[-1]
         plan['feat'] = feat
-        produced0 = {id(f_.buf): 0 for f_ in feats}
-        knobs, dcn_launches = self._tune_dcn_schedule(dcn_layers, produced0, N, H, W, dev, tune)
+        knobs, dcn_launches = self._tune_dcn_schedule(dcn_layers, dcn_views, N, H, W, dev, tune)
         plan['dcn_knobs'] = knobs
-        plan['dcn_layers'] = {ly.name: (ly.up[3] if ly.up is not None else ly.out) for ly in dcn_layers}   # name -> result view
+        plan['dcn_layers'] = {v.name: (v.up[3] if v.up is not None else v.out) for v in dcn_views.values()}   # name -> result view
         L.extend(dcn_launches)
 
         small, big = P['heads_small'], P['heads_big']
@@ -543,180 +541,63 @@ class DLASegHIP(torch.nn.Module):
                 _lib.check(rc, l.name)
 
     # --- the 16 DeformConv nodes of DLAUp / IDAUp as grouped launches -------------------------------------
-    def _schedule_dcn(self, layers, produced0, N, dev, knobs, tune=True):
-        """Launch list of the 16 DCN nodes for one choice of ``knobs``.
-
-        Dataflow (dla.py:539-574): a `proj` node only reads a finished level; the IDAUp step behind it needs the
-        previous node's output as its skip tensor; a `node` reads that step's result.  Every layer is split in two
-        launches' worth of work -- MAIN (gather + contraction, results or split-K partials) and FINISH (reduction +
-        BN + ReLU + IDAUp step) -- and placed in the earliest slot t (M_t at time 2t, F_t at time 2t+1) whose
-        inputs exist: main(L) = first t with 2t > time(x); finish(L) = first t' >= main(L) with 2t'+1 > time(skip).
-        The layers sharing a slot go out as ONE ct_dcn_v2_group launch each for M_t and F_t: 8 + 7 launches for the
-        16 nodes instead of 16 + (offset convs) + 8 reductions, and at one stream 768 .. 1536 workgroups per launch
-        instead of 128 .. 512.  knobs = (fuse_max_cin, chunks_per_split, nkk, split_offsets): the offset/mask conv
-        is computed inside the DCN launch for Cin <= fuse_max_cin -- every workgroup of a split-K layer then repeats
-        it over ALL input channels, 47 % of a 256-channel layer's time at one stream -- else ahead of the slot: K-split
-        over 64-channel chunks in ONE CT_DCN_OFFSETS launch for all layers of the slot (split_offsets = 1, one
-        workgroup per 32-pixel tile and chunk whatever Cin; split_offsets = 3, round 6: the same launch as Winograd
-        F(2x2,3x3) tiles, one workgroup per 64-pixel block and chunk) or by one conv launch per layer (0; 2: a Winograd
-        launch per layer writing raw sums); every workgroup
-        contracts chunks_per_split 32-channel chunks, in steps of 16 * nkk channels (nkk = 2 / 4: 16 / 32 MFMAs per
-        wave between barriers).  knobs[4] (round 3) = chunks per split of the SMALL slots: at one stream the three `proj`
-        slots hold 256 .. 384 workgroups of 18 (chunk, tap) steps each on 768 workgroup slots -- one wave per SIMD,
-        nothing to hide the gather latency behind -- while their layers go through the workspace anyway (IDAUp step in
-        the finishing launch); splitting K twice as fine fills the chip and halves every workgroup's loop.  0 = off,
-        2 = two chunks per split, 1 = one chunk per split (then in 32-channel steps).  knobs[5] = 1: the layers of
-        those slots also leave their offset convs to the slot's K-split OFFSETS launch (a fused conv would be repeated
-        by every split)."""
+    def _schedule_dcn(self, layers, views, N, dev, knobs, tune=True):
+        """Launch list of the 16 DCN nodes for one choice of ``knobs``: dcn_schedule.plan decides, this gives every
+        planned layer its offset conv or `part` buffer, its ct_dcn_desc and its workspace, and every planned launch its
+        _Launch.  ``views``: {layer name: _DcnLayer}."""
         lib = _lib.load()
         P = self._prepared
-        fuse_max_cin, cps, nkk = knobs[:3]
-        split_offsets = knobs[3] if len(knobs) > 3 else 1
-        cps_small = knobs[4] if len(knobs) > 4 else 0
-        small_unfuse = knobs[5] if len(knobs) > 5 else 0      # small slots: offset convs out of the MAIN launch too
-        # knobs[6] (round 6) = 1: MAIN launches as persistent launches (ct_dcn_desc.algo 5xxxx / 6xxxx: `dcn_slots` resident
-        # workgroups striding over the pixel tiles of their column, gathers / weights / the next sampling table running
-        # across tile boundaries) wherever every layer of the launch can -- no fused offset conv, an even number of step
-        # units per split; bit-identical to the one-workgroup-per-tile launch
-        persist = knobs[6] if len(knobs) > 6 else 0
-        slot_cps = {}
-        sizes, mains = self._dcn_slot_sizes(layers, produced0, N, cps, with_mains=True)
-        if cps_small and cps_small < cps:
-            for t, wgs in sizes.items():
-                if wgs < SMALL_SLOT_WGS:
-                    slot_cps[t] = cps_small
-        # knobs[5] == 2: every slot that needs an OFFSETS launch anyway (a layer above the fuse threshold) leaves ALL its
-        # offset convs to that launch -- a fused conv is repeated by every cout block and split of its layer
-        unfuse_slots = set()
-        if small_unfuse == 2:
-            unfuse_slots = {m for ly, m in zip(layers, mains) if not (ly.x.C % 64 == 0 and ly.x.C <= fuse_max_cin and FUSE_OFFSET)}
-        time_of = dict(produced0)                    # buffer id -> time after which it is readable
-
-        def t_of(view):
-            return time_of.get(id(view.buf), 0)
-
-        slots = {}
-        convs = {}
-        offs = {}
-        for ly in layers:                            # (reference order: producers come first)
-            pk = P[ly.name]
-            nchunks = ly.x.C // 32
-            ly.main = t_of(ly.x) // 2 + 1
-            c = slot_cps.get(ly.main, cps)
-            # (a finely split layer would repeat a fused offset conv in every split: knobs[5] moves it to the slot's
-            #  K-split OFFSETS launch instead)
-            ly.fused = (ly.x.C % 64 == 0 and ly.x.C <= fuse_max_cin and FUSE_OFFSET
-                        and not (small_unfuse and ly.main in slot_cps) and ly.main not in unfuse_slots)
-            ly.nkk = 2 if (c == 1 or ly.x.C % 64) else nkk
-            ly.splits = max(1, nchunks // c)
+        sched = dcn_schedule.plan(layers, N, knobs, fuse_enabled=FUSE_OFFSET, winograd=WINOGRAD)
+        descs, convs = {}, {}
+        for name, p in sched.layers.items():
+            pk = P[name]
+            _, x, _, out, up = views[name]
             om = part = None
-            raw = False
-            if not ly.fused and split_offsets == 2 and ly.x.C % 64 == 0 and pk['w_off_wino'] is not None:
-                # raw sums by a conv launch of its own, free to use the Winograd shapes (2.25x fewer MFMAs): the bias
-                # and the mask sigmoid are applied by the DCN launch
-                raw = True
-                omv = ops.new_view(N, ly.x.H, ly.x.W, 32, dev)
-                part = omv.buf
-                d = ops.make_conv_desc(ly.x, pk['w_off'], 27, 3, 1, out=omv, w_wino=pk['w_off_wino'])
+            if p.src in ('raw', 'map'):
+                # a conv launch of this layer's own: 'raw' sums free to use the Winograd shapes (the bias and the mask
+                # sigmoid are applied by the DCN launch), or the finished offset/mask map
+                omv = ops.new_view(N, x.H, x.W, 32, dev)
+                if p.src == 'raw':
+                    part = omv.buf
+                    d = ops.make_conv_desc(x, pk['w_off'], 27, 3, 1, out=omv, w_wino=pk['w_off_wino'])
+                else:
+                    om = omv
+                    d = ops.make_conv_desc(x, pk['w_off'], 27, 3, 1, shift=pk['b_off'], out=om, sig=(18, 27))
                 if tune:
                     autotune.tune_conv(d, dev)
-                convs.setdefault(ly.main, []).append(
-                    _Launch(ly.name + '.offset', 'conv', d, (ly.x, omv, pk),
-                            ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-            elif not ly.fused and split_offsets and ly.x.C % 64 == 0:
-                part = torch.empty((ly.x.C // 64) * N * ly.x.H * ly.x.W * 32, dtype=torch.float32, device=dev)
-                offs.setdefault(ly.main, []).append(ly)
-            elif not ly.fused:
-                om = ops.new_view(N, ly.x.H, ly.x.W, 32, dev)
-                d = ops.make_conv_desc(ly.x, pk['w_off'], 27, 3, 1, shift=pk['b_off'], out=om, sig=(18, 27))
-                if tune:
-                    autotune.tune_conv(d, dev)
-                convs.setdefault(ly.main, []).append(
-                    _Launch(ly.name + '.offset', 'conv', d, (ly.x, om, pk),
-                            ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-            own = ly.fused or part is not None
-            dd = ops.make_dcn_desc(ly.x, om, pk['w'], ly.cout, pk['scale'], pk['shift'], True, ly.out, up=ly.up,
-                                   split_k=ly.splits, algo=3264, om_partial=part, raw_offsets=raw,
+                convs[name] = _Launch(name + '.offset', 'conv', d, (x, omv, pk),
+                                      ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d)))
+            elif p.src != 'fused':                   # ('parts' / 'wino': written by the slot's OFFSETS launch)
+                part = torch.empty((x.C // 64) * N * x.H * x.W * 32, dtype=torch.float32, device=dev)
+            own = p.src != 'map'
+            dd = ops.make_dcn_desc(x, om, pk['w'], p.layer.cout, pk['scale'], pk['shift'], True, out, up=up,
+                                   split_k=p.splits, algo=3264, om_partial=part, raw_offsets=p.src == 'raw',
                                    w_off=pk['w_off'] if own else None, b_off=pk['b_off'] if own else None,
-                                   # split_offsets == 3 (round 6): the slot's K-split OFFSETS launch in its Winograd form
-                                   w_off_wino=pk['w_off_wino'] if (split_offsets == 3 and not ly.fused) else None)
+                                   w_off_wino=pk['w_off_wino'] if p.src == 'wino' else None)
             need_c = ctypes.c_size_t(0)
-            _lib.check(lib.ct_dcn_v2_group_plan(ctypes.byref(dd), ctypes.byref(need_c), None), 'DCN layer ' + ly.name)
+            _lib.check(lib.ct_dcn_v2_group_plan(ctypes.byref(dd), ctypes.byref(need_c), None), 'DCN layer ' + name)
             need = need_c.value
-            ly.use_ws = need > 0
-            keep = [ly.x, om, part, ly.out, pk, ly.up]
+            if (need > 0) != p.use_ws:
+                raise _lib.CTError('DCN layer %s: the library wants %d workspace bytes, the schedule planned %s'
+                                   % (name, need, 'a workspace' if p.use_ws else 'none'))
+            keep = [x, om, part, out, pk, up]
             if need:
                 ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
                 dd.workspace, dd.workspace_bytes = ws.data_ptr(), need
                 keep.append(ws)
-            ly.desc = (dd, keep)
-            if ly.use_ws:
-                ly.finish = max(ly.main, (t_of(ly.up[2]) + 1) // 2) if ly.up is not None else ly.main
-                done = 2 * ly.finish + 1
-            else:
-                ly.finish = None
-                done = 2 * ly.main
-            time_of[id((ly.up[3] if ly.up is not None else ly.out).buf)] = done
-            slots.setdefault(ly.main, {'main': [], 'finish': []})['main'].append(ly)
-            if ly.finish is not None:
-                slots.setdefault(ly.finish, {'main': [], 'finish': []})['finish'].append(ly)
-        out = []
-
-        def group(lys, phases, tag):
-            if phases == _lib.CT_DCN_MAIN:
-                # longest workgroups first (round 6): the dispatcher hands out workgroups in id order, so the layer whose
-                # workgroups run the most (chunk, tap) steps starts first and the short ones fill the tail of the launch
-                lys = sorted(lys, key=lambda ly: -((ly.x.C // 32 + ly.splits - 1) // ly.splits))
-            for i in range(0, len(lys), 4):
-                part = lys[i:i + 4]
-                arr = (_lib.DcnDesc * len(part))()
-                keep = []
-                def can_persist(ly):
-                    cpsplit = -(-(ly.x.C // 32) // ly.splits)
-                    return (not ly.fused and (ly.x.C // 32) % cpsplit == 0
-                            and cpsplit % (4 if ly.nkk == 4 else 2) == 0)
-                pers = bool(persist) and phases == _lib.CT_DCN_MAIN and all(can_persist(ly) for ly in part)
-                for j, ly in enumerate(part):
-                    ctypes.memmove(ctypes.byref(arr[j]), ctypes.byref(ly.desc[0]), ctypes.sizeof(_lib.DcnDesc))
-                    arr[j].algo = (43264 if ly.nkk == 4 else 3264) + (20000 if pers and ly.nkk == 4 else 50000 if pers else 0)
-                    keep.append(ly.desc[1])
-                name = '%s[%s]' % (tag, ' + '.join(ly.name for ly in part))
-                out.append(_Launch(name, 'dcn_group', (arr, len(part), phases), keep))
-
-        for t in sorted(slots):
-            out.extend(convs.get(t, []))
-            if offs.get(t):
-                group(offs[t], _lib.CT_DCN_OFFSETS, 'dcn.offsets')
-            lys = slots[t]['main']
-            if lys:
-                group(lys, _lib.CT_DCN_MAIN, 'dcn')
-            if slots[t]['finish']:
-                group(slots[t]['finish'], _lib.CT_DCN_FINISH, 'dcn.finish')
-        return out
-
-    @staticmethod
-    def _dcn_slot_sizes(layers, produced0, N, cps, with_mains=False):
-        """{MAIN slot: workgroups} of the schedule with ``cps`` chunks per split everywhere.  A split layer is readable
-        one time step later, which rounds to the same next MAIN slot for a consumer that READS it; only a `proj` node
-        whose SKIP input comes from a split layer finishes one slot later (at 512x512: ida_up.node_1/2 move from slots
-        7/8 to 8/10 when the 64-channel nodes are split, cps = 1)"""
-        time_of = dict(produced0)
-        sizes = {}
-        mains = []
-        for ly in layers:
-            main = time_of.get(id(ly.x.buf), 0) // 2 + 1
-            mains.append(main)
-            splits = max(1, (ly.x.C // 32) // cps)
-            use_ws = splits > 1 or ly.up is not None
-            if use_ws:
-                fin = max(main, (time_of.get(id(ly.up[2].buf), 0) + 1) // 2) if ly.up is not None else main
-                done = 2 * fin + 1
-            else:
-                done = 2 * main
-            time_of[id((ly.up[3] if ly.up is not None else ly.out).buf)] = done
-            tiles = N * ((ly.x.H + 1) // 2) * ((ly.x.W + 15) // 16) * ((ly.cout + 63) // 64)
-            sizes[main] = sizes.get(main, 0) + tiles * splits
-        return (sizes, mains) if with_mains else sizes
+            descs[name] = (dd, keep)
+        launches = []
+        for l in sched.launches:
+            if l.tag == 'conv':
+                launches.append(convs[l.names[0]])
+                continue
+            arr = (_lib.DcnDesc * len(l.names))()
+            for j, (name, algo) in enumerate(zip(l.names, l.algos)):
+                ctypes.memmove(ctypes.byref(arr[j]), ctypes.byref(descs[name][0]), ctypes.sizeof(_lib.DcnDesc))
+                arr[j].algo = algo
+            launches.append(_Launch('%s[%s]' % (l.tag, ' + '.join(l.names)), 'dcn_group', (arr, len(l.names), l.phase),
+                                    [descs[name][1] for name in l.names]))
+        return launches
 
     def _time_launches(self, launches, reps=10):
         """device time (us) of a launch list, by graph replay on a side stream"""
@@ -751,72 +632,52 @@ class DLASegHIP(torch.nn.Module):
         del g
         return best
 
-    def _tune_dcn_schedule(self, layers, produced0, N, H, W, dev, tune):
-        """Pick the knobs of _schedule_dcn for this (batch, size) by timing the whole 16-node sequence (a HIP graph of
-        exactly its launches) for every candidate; the choice is cached like the per-layer ones (pinned table /
-        CENTERTRACK_TUNE_CACHE) because it fixes the fp32 summation order.  CENTERTRACK_DCN_KNOBS="a,b,c" forces one."""
+    def _tune_dcn_schedule(self, layers, views, N, H, W, dev, tune):
+        """Pick the knobs of the DCN schedule for this (batch, size) by timing the whole 16-node sequence (a HIP graph of
+        exactly its launches) for every candidate of dcn_schedule.knob_grid; the choice is cached like the per-layer ones
+        (pinned table / CENTERTRACK_TUNE_CACHE) because it fixes the fp32 summation order.  CENTERTRACK_DCN_KNOBS="a,b,c"
+        forces one."""
         env = os.environ.get('CENTERTRACK_DCN_KNOBS', '')
         if env:
             knobs = tuple(int(v) for v in env.split(','))
-            return knobs, self._schedule_dcn(layers, produced0, N, dev, knobs, tune)
-        default = (128, 4, 2, 1, 0, 0, 0)
+            return knobs, self._schedule_dcn(layers, views, N, dev, knobs, tune)
         if not tune:
-            return default, self._schedule_dcn(layers, produced0, N, dev, default, tune)
-        key = 'dcnplan5:%d,%d,%d' % (N, H, W)
-        key4 = 'dcnplan4:%d,%d,%d' % (N, H, W)          # (tables before the persistent launches: six knobs)
-        key3 = 'dcnplan3:%d,%d,%d' % (N, H, W)          # (round-2 tables: four knobs, no fine-split slots)
+            knobs = (128, 4, 2, 1, 0, 0, 0)
+            return knobs, self._schedule_dcn(layers, views, N, dev, knobs, tune)
+        # dcnplan4: tables before the persistent launches (six knobs); dcnplan3: four knobs, no fine-split slots
+        key, older = 'dcnplan5:%d,%d,%d' % (N, H, W), ('dcnplan4:%d,%d,%d' % (N, H, W), 'dcnplan3:%d,%d,%d' % (N, H, W))
         autotune._load_file()
-        retune = os.environ.get('CENTERTRACK_DCN_RETUNE', '0') == '1'      # (tools/retune_dcn.py: measure again)
-        if key in autotune._CACHE and not retune:
-            knobs = tuple(int(v) for v in autotune._CACHE[key][:-1])
-            return knobs, self._schedule_dcn(layers, produced0, N, dev, knobs)
-        if key4 in autotune._CACHE and not retune:
-            knobs = tuple(int(v) for v in autotune._CACHE[key4][:-1]) + (0,)
-            return knobs, self._schedule_dcn(layers, produced0, N, dev, knobs)
-        if key3 in autotune._CACHE and not retune:
-            knobs = tuple(int(v) for v in autotune._CACHE[key3][:4]) + (0, 0, 0)
-            return knobs, self._schedule_dcn(layers, produced0, N, dev, knobs)
+        if os.environ.get('CENTERTRACK_DCN_RETUNE', '0') != '1':           # (tools/retune_dcn.py: measure again)
+            for k in (key,) + older:
+                if k in autotune._CACHE:
+                    knobs = dcn_schedule.normalize(autotune._CACHE[k][:-1])
+                    return knobs, self._schedule_dcn(layers, views, N, dev, knobs)
+        verbose = os.environ.get('CENTERTRACK_TUNE_VERBOSE')
         best = None
         tried = []
-        # (split_offsets = 0 -- one conv launch per un-fused layer -- never won in round 2's sweeps: 368 against 336 us
-        # at one stream, 1932 against 1818 us at eight; it stays reachable through CENTERTRACK_DCN_KNOBS.  Neither did
-        # 128-cout tiles for the layers with >= 128 couts in a MAIN launch of their own: 6866 against 6830 us at 32
-        # streams, 1826 against 1806 at eight -- the second launch per slot costs what the wider tile gains)
-        for fuse_max in (0, 64, 128, 256):
-            for cps in (2, 4, 8):
-                for nkk in (2, 4):
-                    for so in ((1, 2, 3) if fuse_max < 256 else (1,)):
-                        small = [t for t, w in self._dcn_slot_sizes(layers, produced0, N, cps).items() if w < SMALL_SLOT_WGS]
-                        for cs, un in (((0, 0), (0, 2)) + tuple((c, u) for c in (2, 1) if c < cps for u in (0, 1, 2)) if small
-                                       else ((0, 0), (0, 2))):
-                            knobs = (fuse_max, cps, nkk, so, cs, un, 0)
-                            launches = self._schedule_dcn(layers, produced0, N, dev, knobs)
-                            us = self._time_launches(launches)
-                            if os.environ.get('CENTERTRACK_TUNE_VERBOSE'):
-                                print('dcn schedule N=%d %dx%d knobs %s: %d launches, %.1f us' % (N, H, W, knobs, len(launches), us))
-                            tried.append((us, knobs))
-                            if best is None or us < best[0]:
-                                best = (us, knobs)
-                            del launches
-        # second stage (CENTERTRACK_DCN_TUNE_PERSIST=1): the persistent MAIN launches on top of the five best schedules and of
-        # every schedule that keeps all offset convs out of the MAIN launches (the only layers a persistent launch takes).
-        # Off by default: over the 28 pinned shapes the persistent form lost everywhere, by 1 .. 8 %
-        # (profiles/r06_z_persistent_vs_per_tile_all_shapes.txt)
-        tried.sort()
+        for knobs in dcn_schedule.knob_grid(layers, N):
+            launches = self._schedule_dcn(layers, views, N, dev, knobs)
+            us = self._time_launches(launches)
+            if verbose:
+                print('dcn schedule N=%d %dx%d knobs %s: %d launches, %.1f us' % (N, H, W, knobs, len(launches), us))
+            tried.append((us, knobs))
+            if best is None or us < best[0]:
+                best = (us, knobs)
+            del launches
+        # second stage (dcn_schedule.persist_candidates), off unless CENTERTRACK_DCN_TUNE_PERSIST=1
         stage2 = os.environ.get('CENTERTRACK_DCN_TUNE_PERSIST', '0') == '1'
-        for us0, k0 in (tried[:5] + [t for t in tried[5:] if t[1][0] == 0 and t[1][5] == 0]) if stage2 else ():
-            knobs = k0[:6] + (1,)
-            launches = self._schedule_dcn(layers, produced0, N, dev, knobs)
+        for us0, knobs in dcn_schedule.persist_candidates(tried) if stage2 else ():
+            launches = self._schedule_dcn(layers, views, N, dev, knobs)
             if any(l.fn == 'dcn_group' and int(l.args[0][0].algo) >= 50000 for l in launches):
                 us = self._time_launches(launches)
-                if os.environ.get('CENTERTRACK_TUNE_VERBOSE'):
+                if verbose:
                     print('dcn schedule N=%d %dx%d knobs %s: %d launches, %.1f us (%.1f without)' % (N, H, W, knobs, len(launches), us, us0))
                 if us < best[0]:
                     best = (us, knobs)
             del launches
         autotune._CACHE[key] = tuple(best[1]) + (round(best[0], 1),)
         autotune._save_file()
-        return best[1], self._schedule_dcn(layers, produced0, N, dev, best[1])
+        return best[1], self._schedule_dcn(layers, views, N, dev, best[1])
 
     @staticmethod
     def plan_signature(plan):

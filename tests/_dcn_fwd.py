@@ -404,9 +404,9 @@ def dcn_regimes():
         r[('group', 'layers', n)] = 'dcn_mfma.hip: launch_group `for (i = 0; i < n; ++i)`; the kernels `if (i < g.n && bid >= g.first[i]) pi = i`'
     for m in ('in one call', 'in three calls'):
         r[('group', 'phases', m)] = 'dcn_mfma.hip: launch_group `phases & CT_DCN_OFFSETS / MAIN / FINISH`'
-    r[('group', 'a FINISH call on another set of layers than the MAIN call')] = 'model.py: _schedule_dcn slots[t][\'finish\']'
+    r[('group', 'a FINISH call on another set of layers than the MAIN call')] = 'dcn_schedule.py: plan, the FINISH names of a slot'
     r[('group', 'an up layer with splits == 1')] = 'dcn_mfma.hip: make_plan `p->use_ws = (p->splits > 1 || (grouped && d->up_w))`'
-    r[('group', 'layers of different step counts')] = 'model.py: _schedule_dcn group(), sorted by steps; dcn_mfma.hip: per-layer nsteps'
+    r[('group', 'layers of different step counts')] = 'dcn_schedule.py: plan, MAIN names sorted by steps; dcn_mfma.hip: per-layer nsteps'
     r[('group', 'persistent, several layers')] = 'dcn_mfma.hip: launch_group, the bisection over `slots` and `per_col`'
     for v in (64, 128):
         r[('dcn_bn', v)] = 'dcn_mfma.hip: make_plan `ct_tune_get(CT_TUNE_DCN_BN)`'
@@ -682,7 +682,8 @@ def mutants64(case):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the production schedule, restated (model.py: the IDAUp tree of _build_plan, _dcn_slot_sizes, _schedule_dcn)
+# the production schedule, restated (model.py: the IDAUp tree of _build_plan; dcn_schedule.py: slot_sizes, plan).  It imports nothing
+# of the package: tests/test_dcn_forward_cpu.py holds dcn_schedule.plan against it
 
 CHANNELS = [16, 32, 64, 128, 256, 512]
 SMALL_SLOT_WGS = 600
@@ -738,7 +739,7 @@ def _slot_sizes(layers, N, cps):
 
 
 def neck_schedule(knobs, N, H, W, fuse_enabled=True):
-    """what _schedule_dcn gives each neck layer for a knob tuple, and its group launches in order:
+    """what dcn_schedule.plan gives each neck layer for a knob tuple, and its group launches in order:
     [(tag, [layer names], phases, [(algo, split_k, fuse_offset)])], plus {name: dict(algo, split_k, fuse_offset, up_f, src, layer)}"""
     knobs = tuple(knobs) + (1, 0, 0, 0)[len(knobs) - 3:] if len(knobs) < 7 else tuple(knobs)
     fuse_max, cps, nkk, split_offsets, cps_small, small_unfuse, persist = knobs[:7]

@@ -431,7 +431,8 @@ def _pinned_schedules():
 
 
 def _knob_grid(N, H, W):
-    """the tuples model.py::_tune_dcn_schedule walks, with the persistent second stage on top of every one of them"""
+    """the tuples model.py::_tune_dcn_schedule walks (restated: dcn_schedule.knob_grid is held against this), with the persistent
+    second stage on top of every one of them"""
     layers = D.neck_layers(H, W)
     for fuse_max in (0, 64, 128, 256):
         for cps in (2, 4, 8):
@@ -444,8 +445,8 @@ def _knob_grid(N, H, W):
 
 
 def test_production_schedules_reach_only_tested_regimes():
-    """the 16 neck layers as model.py::_schedule_dcn launches them (restated: tests/_dcn_fwd.py::neck_schedule, held against the model's
-    plan_signature by tests/test_hip_dcn_forward.py) for every pinned dcnplan4 / dcnplan5 entry and for the tuner's whole knob grid at
+    """the 16 neck layers as the model launches them (restated: tests/_dcn_fwd.py::neck_schedule, held against dcn_schedule.plan below
+    and against the model's plan_signature by tests/test_hip_dcn_forward.py) for every pinned dcnplan4 / dcnplan5 entry and for the tuner's whole knob grid at
     the pinned sizes"""
     reached = D.all_keys(D.GPU_CASES, D.GROUPS)
     pinned = _pinned_schedules()
@@ -463,3 +464,114 @@ def test_production_schedules_reach_only_tested_regimes():
             assert keys <= reached, ((N, H, W), knobs, sorted(keys - reached, key=str))
             n += 1
     assert n > 5000
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the planner the model, the tuner and the tools use (centertrack_amd/dcn_schedule.py) against the restatement above
+
+def _planner_layers(H, W):
+    from centertrack_amd import dcn_schedule as S
+    return [S.Layer(*ly) for ly in D.neck_layers(H, W)]
+
+
+def _grid_both_ways(layers, N):
+    """the tuner's first stage, each tuple also with split_offsets = 0 once, all of them without and with persistent launches"""
+    from centertrack_amd import dcn_schedule as S
+    for k in S.knob_grid(layers, N):
+        for so in ((k[3], 0) if k[3] == 1 else (k[3],)):
+            for persist in (0, 1):
+                yield k[:3] + (so,) + k[4:6] + (persist,)
+
+
+def _same_schedule(sched, launches, info, what):
+    got = [(l.tag, list(l.names), l.phase, [(a, sched.layers[n].splits, D.FUSE_OFFSET[sched.layers[n].src]) for a, n in zip(l.algos, l.names)])
+           for l in sched.launches if l.tag != 'conv']
+    assert got == launches, what
+    assert list(sched.layers) == list(info), what
+    for name, p in sched.layers.items():
+        i = info[name]
+        assert (p.main, p.finish, p.fused, p.src, p.nkk, p.splits) == (i['main'], i['finish'], i['fused'], i['src'], i['nkk'], i['split_k']), (what, name)
+
+
+def test_the_planner_is_the_restated_schedule():
+    """dcn_schedule.plan on the 16 neck layers equals neck_schedule -- group launches as (tag, names, phase, (algo, split_k,
+    fuse_offset)), per layer main / finish / fused / src / nkk / split_k -- for every pinned entry and for the tuner's grid, with
+    split_offsets = 0 and the persistent stage on top, at every pinned size"""
+    from centertrack_amd import dcn_schedule as S
+    pinned = _pinned_schedules()
+    for key, N, H, W, knobs in pinned:
+        _same_schedule(S.plan(_planner_layers(H, W), N, knobs), *D.neck_schedule(knobs, N, H, W), what=(key, knobs))
+    n = 0
+    for N, H, W in sorted(set(p[1:4] for p in pinned)):
+        layers = _planner_layers(H, W)
+        for knobs in _grid_both_ways(layers, N):
+            sched = S.plan(layers, N, knobs)
+            launches, info = D.neck_schedule(knobs, N, H, W)
+            _same_schedule(sched, launches, info, ((N, H, W), knobs))
+            assert S.signature(sched) == D.schedule_signature(launches)
+            n += 1
+    assert n > 20000
+    # the switch the package passes for CENTERTRACK_FUSE_OFFSET=0
+    for knobs in ((128, 4, 2, 1, 0, 0, 0), (256, 8, 4, 1, 2, 2, 0)):
+        _same_schedule(S.plan(_planner_layers(512, 512), 1, knobs, fuse_enabled=False), *D.neck_schedule(knobs, 1, 512, 512, fuse_enabled=False), what=knobs)
+
+
+def test_knob_grid_is_the_tuners_first_stage_in_order():
+    from centertrack_amd import dcn_schedule as S
+    for N, H, W in sorted(set(p[1:4] for p in _pinned_schedules())):
+        assert list(S.knob_grid(_planner_layers(H, W), N)) == [k for k in _knob_grid(N, H, W) if k[6] == 0], (N, H, W)
+    # the second stage: the five fastest and every later schedule with all offset convs outside the MAIN launches, persist set
+    tried = [(10.0 + i, (fm, 4, 2, 1, 0, un, 0)) for i, (fm, un) in enumerate([(128, 0), (0, 2), (64, 0), (0, 0), (256, 0), (128, 2), (0, 0), (0, 1), (64, 2)])]
+    got = S.persist_candidates(list(reversed(tried)))
+    assert got == [(us, k[:6] + (1,)) for us, k in tried[:5] + [tried[6]]]
+
+
+def test_normalize_reads_every_table_generation():
+    from centertrack_amd import dcn_schedule as S
+    assert S.normalize((128, 4, 2)) == (128, 4, 2, 1, 0, 0, 0)
+    assert S.normalize([64, 8, 4, 0]) == (64, 8, 4, 0, 0, 0, 0)
+    assert S.normalize((0, 4, 4, 3, 2, 1)) == (0, 4, 4, 3, 2, 1, 0)
+    assert S.normalize((0, 4, 2, 1, 0, 0, 1)) == (0, 4, 2, 1, 0, 0, 1)
+    assert S.normalize((128.0, 4.0, 2.0, 1.0, 0.0, 0.0)) == (128, 4, 2, 1, 0, 0, 0) and all(type(v) is int for v in S.normalize((128.0, 4.0, 2.0)))
+
+
+def test_the_planners_workspace_and_persist_rules_are_the_librarys(lib):
+    """over every distinct (Cin, splits, nkk, fused, up) the grid reaches at the pinned sizes: ct_dcn_v2_group_plan reports workspace
+    bytes exactly where the planner says use_ws, and accepts the persistent algo exactly where can_persist holds"""
+    from centertrack_amd import dcn_schedule as S
+    keep, ptr = _ptr()
+    combos = {}
+    for N, H, W in sorted(set(p[1:4] for p in _pinned_schedules())):
+        layers = _planner_layers(H, W)
+        for knobs in _grid_both_ways(layers, N):
+            for p in S.plan(layers, N, knobs).layers.values():
+                combos.setdefault((p.layer.Cin, p.splits, p.nkk, p.fused, p.layer.up is not None), (N, p))
+    assert len(set(c[:4] for c in combos)) == 37 and any(c[4] for c in combos)
+    for (Cin, splits, nkk, fused, up), (N, p) in sorted(combos.items()):
+        ly, fo = p.layer, S.FUSE_OFFSET[p.src]
+        need = ctypes.c_size_t(0)
+        d = _desc(ptr, N, ly.H, ly.W, Cin, ly.cout, 3264, splits, fo, ly.up[0] if up else 0)
+        assert lib.ct_dcn_v2_group_plan(ctypes.byref(d), ctypes.byref(need), None) == 0, (ly.name, lib.ct_last_error())
+        assert (need.value > 0) == p.use_ws, (Cin, splits, nkk, fused, up, need.value)
+        d = _desc(ptr, N, ly.H, ly.W, Cin, ly.cout, 63264 if nkk == 4 else 53264, splits, fo, ly.up[0] if up else 0)
+        rc = lib.ct_dcn_v2_group_plan(ctypes.byref(d), None, None)
+        assert (rc == 0) == S.can_persist(Cin, splits, nkk, fused), (Cin, splits, nkk, fused, up, rc, lib.ct_last_error())
+
+
+@pytest.mark.parametrize('split_offsets', [0, 2])
+def test_offset_convs_run_ahead_of_their_slots_groups(split_offsets):
+    """one `.offset` conv entry per un-fused layer, in layer order, ahead of the OFFSETS / MAIN / FINISH groups of the layer's slot"""
+    from centertrack_amd import dcn_schedule as S
+    N, H, W = 1, 512, 512
+    layers = _planner_layers(H, W)
+    for knobs in ((128, 4, 2, split_offsets, 0, 0, 0), (0, 4, 4, split_offsets, 2, 1, 1), (64, 8, 4, split_offsets, 1, 2, 0)):
+        sched = S.plan(layers, N, knobs)
+        launches, info = D.neck_schedule(knobs, N, H, W)
+        want = []
+        for t in sorted(set(i['main'] for i in info.values()) | set(i['finish'] for i in info.values() if i['finish'] is not None)):
+            want += [('conv', (ly.name,)) for ly in layers if info[ly.name]['main'] == t and not info[ly.name]['fused']]
+            want += [(tag, tuple(names)) for tag, names, phase, _ in launches if info[names[0]]['finish' if phase == 2 else 'main'] == t]
+        assert [(l.tag, l.names) for l in sched.launches] == want, knobs
+        convs = [l for l in sched.launches if l.tag == 'conv']
+        assert convs and all(l.phase == 0 and l.algos == () for l in convs)
+        assert all(p.src == ('fused' if p.fused else 'raw' if split_offsets else 'map') for p in sched.layers.values())

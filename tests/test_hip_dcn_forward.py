@@ -271,13 +271,15 @@ def test_dcn_rot_workgroups_equal_the_images_launched_one_by_one(device):
 # ---------------------------------------------------------------------------------------------------------------------
 # the real schedule: keeps tests/_dcn_fwd.py::neck_schedule (and with it test_production_schedules_reach_only_tested_regimes) honest
 
-# between them: split_offsets 1, 2 and 3, nkk 2 and 4, fine-split small slots with and without their offset convs moved out, persistent
-SCHEDULE_KNOBS = [(128, 4, 2, 1, 0, 0, 0), (0, 4, 4, 3, 2, 1, 0), (64, 8, 4, 2, 1, 2, 0), (0, 4, 2, 1, 0, 0, 1), (0, 4, 4, 1, 0, 0, 1)]
+# between them: split_offsets 0, 1, 2 and 3 (every offset source), nkk 2 and 4, fine-split small slots with and without their offset
+# convs moved out, persistent
+SCHEDULE_KNOBS = [(128, 4, 2, 1, 0, 0, 0), (0, 4, 4, 3, 2, 1, 0), (64, 8, 4, 2, 1, 2, 0), (0, 4, 2, 1, 0, 0, 1), (0, 4, 4, 1, 0, 0, 1),
+                  (128, 4, 2, 0, 0, 0, 0)]
 
 
 @pytest.mark.parametrize('knobs', SCHEDULE_KNOBS, ids=lambda k: '-'.join(str(v) for v in k))
 def test_the_models_dcn_schedule_is_the_restated_one(device, monkeypatch, knobs):
-    from centertrack_amd import weights as Wt
+    from centertrack_amd import dcn_schedule as S, weights as Wt
     from centertrack_amd.model import DLASegHIP
     N, H, W = 1, 64, 96
     monkeypatch.setenv('CENTERTRACK_DCN_KNOBS', ','.join(str(v) for v in knobs))
@@ -290,5 +292,21 @@ def test_the_models_dcn_schedule_is_the_restated_one(device, monkeypatch, knobs)
     got = [s for s in DLASegHIP.plan_signature(plan).split(';') if ':dcn:' in s]
     launches, info = D.neck_schedule(knobs, N, H, W)
     assert got == D.schedule_signature(launches), '\n'.join(['model:'] + got + ['restated:'] + D.schedule_signature(launches))
+    # ... and the planner's (centertrack_amd/dcn_schedule.py), which the CPU tests hold against the restatement on the whole grid
+    sched = S.plan([S.Layer(*ly) for ly in D.neck_layers(H, W)], N, knobs)
+    assert got == S.signature(sched)
+    assert [l.name for l in plan['launches'] if l.name.endswith('.offset')] == [l.names[0] + '.offset' for l in sched.launches if l.tag == 'conv']
+    # every DCN descriptor has a workspace exactly where the planner said so
+    seen = set()
+    for l in plan['launches']:
+        if l.fn == 'dcn_group':
+            arr, n, _ = l.args
+            for j, name in enumerate(l.name[l.name.index('[') + 1:-1].split(' + ')):
+                has = bool(arr[j].workspace) and arr[j].workspace_bytes > 0
+                assert has == sched.layers[name].use_ws and has == (info[name]['finish'] is not None), (l.name, name)
+                seen.add(name)
+    assert seen == set(sched.layers) and len(seen) == 16
+    if knobs[3] == 0:
+        assert any(p.src == 'map' for p in sched.layers.values()), 'no offset/mask map written by a conv launch in this schedule'
     if knobs[6]:
         assert any(t[0] >= 50000 for _, _, ph, triples in launches if ph == MAIN for t in triples), 'no persistent launch in this schedule'
