@@ -107,6 +107,24 @@ def imread_bgr(path):
         return np.ascontiguousarray(np.asarray(im.convert('RGB'))[:, :, ::-1])
 
 
+def _prefetchable(prefetch, shape):
+    """may ``prefetch`` be uploaded ahead into a frame slot: a contiguous float32 host tensor of the frames' ``shape``"""
+    return (prefetch is not None and torch.is_tensor(prefetch) and prefetch.device.type == 'cpu'
+            and prefetch.dtype == torch.float32 and prefetch.is_contiguous() and tuple(prefetch.shape) == tuple(shape))
+
+
+def _frame_source(images, uploaded, slot):
+    """where this step's frame comes from, as a ``FrameStepArgs.frame_kind``: already in ``slot``, one DMA from a host or a
+    device tensor, or a torch copy.  ``uploaded``: (tensor, version, slot) of the previous step's prefetch, or None."""
+    # the SAME tensor object, unmodified since it was handed over (an in-place edit bumps ``_version``; a new
+    # tensor at a recycled address is another object), uploaded into THIS slot
+    if uploaded is not None and uploaded[0] is images and uploaded[1] == images._version and uploaded[2] == slot:
+        return _lib.CT_FRAME_UPLOADED
+    if images.dtype == torch.float32 and images.is_contiguous():
+        return _lib.CT_FRAME_DEVICE if images.device.type == 'cuda' else _lib.CT_FRAME_HOST
+    return _lib.CT_FRAME_IN_PLACE
+
+
 class _HipGraph(object):
     """One captured frame (ct_graph_begin / ct_graph_end); ``replay()`` enqueues it on the current stream."""
 
@@ -136,6 +154,272 @@ class _HipGraph(object):
             self._lib.ct_graph_destroy(self.exec)
         except Exception:
             pass
+
+
+class _FrameContext(object):
+    """What a ``StreamDetector`` keeps per network input size: launch plan, static buffers, captured graphs, native frame
+    loop.  It refers back to its detector (model, options, trackers), so the two form a reference cycle: a dropped
+    detector is destroyed by the cyclic collector, which ``_lib.capture_guard`` keeps out of captures."""
+    _METHODS = ('pre_stage', 'device_frame')
+    __slots__ = ('det', 'hw', 'NB', 'plan', 'img_in', 'hm_in', 'render', 'flip_call', 'merged', 'done_flag', 'host_out',
+                 'host_rows', 'decoder', 'row_layout', 'host_hm', 'max_blobs', 'pc_host', 'pc_dev', 'prm_host', 'cnt_host',
+                 'prm_dev', 'cnt_dev', 'nslots', 'frames', 'slot', 'launched', 'partial', 'graphs', 'graph', 'raw',
+                 'copy_stream', 'frame_ready', 'copy_sp', 'loop', 'loop_desc', 'loop_stream', 'loop_trackers', 'rows_keep',
+                 'res_cap', 'res_buf', 'counts', 'tin', 'tinv', 'args')
+
+    def __init__(self, det, H, W):
+        tracking = bool(getattr(det.opt, 'tracking', False))
+        with_img = tracking and bool(getattr(det.opt, 'pre_img', True))
+        with_hm = tracking and bool(getattr(det.opt, 'pre_hm', False))
+        # detector, input size, image batch, launch plan and its prior inputs; is the prior heat map rendered from blobs
+        self.det, self.hw, self.NB = det, (H, W), det.B * (2 if det.flip else 1)
+        self.plan = det.model.get_plan(self.NB, H, W, with_img, with_hm, True, det.sparse)
+        (_, self.img_in, self.hm_in), self.render = self.plan['inputs'], det.native and with_hm
+        # flip_test: the arguments of ct_flip_merge; the maps the decode reads (the plan's outputs without flip_test)
+        self.flip_call, self.merged = None, self.plan['outputs']
+        # decode: pinned flag and rows [B,K,F] (tensor, numpy view), decoder, native row layout, heat map of the Python host path
+        self.done_flag = self.host_out = self.host_rows = self.decoder = self.row_layout = self.host_hm = None
+        # blobs of the device-rendered prior heat map: triples of every stream + per-stream counts, host and device
+        self.max_blobs = self.pc_host = self.pc_dev = self.prm_host = self.cnt_host = self.prm_dev = self.cnt_dev = None
+        # rotating frame slots, slot of the NEXT frame, the frame the native loop launched ahead, split-stem maps per slot
+        self.nslots = self.frames = self.launched = self.partial = None
+        self.slot = 0
+        # one captured graph per slot (None: eager launches), the first of them, raw HIP graphs or torch's (``capture``)
+        self.graphs, self.graph, self.raw = None, None, False
+        # upload stream of the Python frame loop with its event and raw handle, from the first prefetch on (``own_copy_stream``)
+        self.copy_stream = self.frame_ready = self.copy_sp = None
+        # the native frame loop and what it reads and writes through pointers (``make_loop``)
+        self.loop = self.loop_desc = self.loop_stream = self.loop_trackers = self.rows_keep = None
+        self.res_cap = self.res_buf = self.counts = self.tin = self.tinv = self.args = None
+        if det.flip:
+            self._build_flip_merge()
+        self._build_decoder(with_hm)
+        if self.render:
+            self._build_blobs()
+        self._build_slots()
+
+    # bench.py, tools/ and the GPU tests read the context by subscript and bench.py cannot change: that is the only reason
+    # for these two.  Inside the package use the attributes.
+    def __getitem__(self, name):
+        if name in self.__slots__ or name in self._METHODS:
+            return getattr(self, name)
+        raise KeyError(name)
+
+    def get(self, name, default=None):
+        return getattr(self, name) if name in self.__slots__ or name in self._METHODS else default
+
+    def _build_flip_merge(self):
+        """detector.py:311-332: averaged heads get a merged [B,c,h,w] map (ct_flip_merge, one launch for all of
+        them); the heads the reference takes from the un-flipped image alone are read in place (first B images)"""
+        B, outs = self.det.B, self.plan['outputs']
+        modes = {'hps': _lib.CT_FLIP_JOINT_OFFSETS, 'hm_hp': _lib.CT_FLIP_JOINTS}
+        modes.update({k: _lib.CT_FLIP_AVG for k in AVERAGE_FLIPS})
+        modes.update({k: _lib.CT_FLIP_NEG_EVEN for k in NEG_AVERAGE_FLIPS})
+        merged, fl = {}, []
+        for k, v in outs.items():
+            if k in modes:
+                merged[k] = torch.empty((B,) + tuple(v.shape[1:]), device=self.det.device)
+                fl.append((v, merged[k], modes[k]))
+            else:
+                merged[k] = v[:B]
+        heads_arr = (_lib.FlipHead * len(fl))()
+        for i, (v, m, mode) in enumerate(fl):
+            assert v.stride(3) == 1 and v.stride(2) == v.shape[3] and v.stride(1) == v.shape[2] * v.shape[3]
+            heads_arr[i].src, heads_arr[i].dst = v.data_ptr(), m.data_ptr()
+            heads_arr[i].src_batch_stride, heads_arr[i].C, heads_arr[i].mode = v.stride(0), v.shape[1], mode
+        pairs = np.ascontiguousarray(getattr(self.det.opt, 'flip_idx', COCO_FLIP_IDX), np.int32).reshape(-1, 2)
+        self.flip_call = (heads_arr, len(fl), pairs, int(outs['hm'].shape[2]), int(outs['hm'].shape[3]))
+        self.merged = merged
+
+    def _build_decoder(self, with_hm):
+        """the decode over the merged maps, its pinned rows and end-of-frame flag (detector.py:338-350 as one block)"""
+        det, opt, merged = self.det, self.det.opt, self.merged
+        dec_heads = {k: v for k, v in merged.items() if k != 'hm'}
+        self.done_flag = torch.zeros((16,), dtype=torch.int32).pin_memory()      # (its own cache line)
+        sparse = self.plan.get('sparse')
+        if sparse is not None:
+            sparse = dict(sparse, zero_tracking=bool(getattr(opt, 'zero_tracking', False)), flip=det.flip)
+        F = ops.Decoder.row_floats(dec_heads, [n for n, *_ in sparse['heads']] if sparse else None)
+        self.host_out = torch.zeros((merged['hm'].shape[0], opt.K, F), dtype=torch.float32).pin_memory()
+        # (round 3: the decode stores its rows straight into the pinned block and raises the end-of-frame flag itself --
+        #  no D2H copy node and no flag kernel at the end of the frame graph; not with pose heads, whose kernels
+        #  complete the rows after the decode)
+        direct = HOST_FLAG and HOST_ROWS
+        self.decoder = ops.Decoder(merged['hm'], dec_heads, opt.K, host_out=self.host_out if direct else None,
+                                   done_flag=self.done_flag if direct else None, sparse=sparse)
+        assert tuple(self.decoder.out.shape) == tuple(self.host_out.shape)
+        self.host_rows = self.host_out.numpy()
+        if with_hm and not det.native:
+            self.host_hm = torch.zeros((self.NB, 1) + self.hw, dtype=torch.float32).pin_memory()
+        if det.native:
+            self.row_layout = fast_track.row_layout(self.decoder.layout)
+
+    def _build_blobs(self):
+        """blob triples of every stream followed by the per-stream counts: ONE pinned buffer, one H2D per frame"""
+        B = self.det.B
+        nblob = self.max_blobs = fast_track.max_blobs(self.det.opt.K)
+        nprm = B * nblob * 3
+        self.pc_host = torch.zeros((nprm + B,), dtype=torch.int32).pin_memory()
+        self.pc_dev = torch.zeros((nprm + B,), dtype=torch.int32, device=self.det.device)
+        self.prm_host, self.cnt_host = self.pc_host[:nprm].view(B, nblob, 3), self.pc_host[nprm:]
+        self.prm_dev, self.cnt_dev = self.pc_dev[:nprm], self.pc_dev[nprm:]
+
+    def _build_slots(self):
+        """Frame buffers owned by THIS detector (the plan's activation buffers are shared by every detector of
+        the model).  They ROTATE: the frame of step t is written into slot t % nslots and read as `pre_img` from
+        there at step t+1, so the reference's `self.pre_images = images` (detector.py:148) costs no copy; with three
+        slots the frame of step t+1 can be uploaded straight into ITS slot while the graph of step t still reads
+        slots t and t-1 (round 3: no staging buffer, no device-to-device copy between upload and launch); one
+        captured graph per slot."""
+        H, W = self.hw
+        self.nslots = 3 if self.img_in is not None else 2
+        self.frames = [torch.zeros_like(self.plan['inputs'][0]) for _ in range(self.nslots)]
+        self.graphs = [None] * self.nslots
+        if self.img_in is not None and self.hm_in is not None and 0 < self.NB <= SPLIT_STEM_MAX:
+            self.partial = [ops.new_view(self.NB, H, W, 16, self.det.device) for _ in range(self.nslots)]
+
+    def own_copy_stream(self):
+        """the Python frame loop's upload stream, created at the first prefetch"""
+        if self.copy_stream is None:
+            self.copy_stream, self.frame_ready = torch.cuda.Stream(device=self.det.device), torch.cuda.Event()
+            self.copy_sp = ctypes.c_void_p(self.copy_stream.cuda_stream)
+
+    def flip_slot(self, slot, sp=None):
+        """the mirrored half of the batch in ``slot`` (detector.py:224-226), built from the frames already in HBM"""
+        cur, B, (H, W) = self.frames[slot], self.det.B, self.hw
+        _lib.check(_lib.load().ct_flip_images(cur.data_ptr(), cur[B:].data_ptr(), B * 3 * H, W,
+                                              sp if sp is not None else _lib.stream_ptr()), 'ct_flip_images')
+
+    def pre_stage(self, slot):
+        """the part of a frame that does not depend on the tracker: the mirrored half of a flip_test batch and the
+        x / pre_img terms of the stem.  The native loop runs it for frame t+1 behind the graph of frame t."""
+        if self.partial is None:
+            return
+        if self.det.flip:
+            self.flip_slot(slot)
+        self.det.model.run_stem_partial(self.frames[slot], self.frames[(slot - 1) % self.nslots], self.partial[slot])
+
+    def device_frame(self, slot=0, with_copies=False):
+        """all device work of one frame; ``with_copies``: also the H2D of the prior-heat-map blobs and the D2H
+        of the packed detections (fixed pinned buffers), so that a captured frame is ONE graph launch"""
+        det, lib, (H, W), st = self.det, _lib.load(), self.hw, _lib.stream_ptr()
+        cur = self.frames[slot]
+        prev = self.frames[(slot - 1) % self.nslots] if self.img_in is not None else None
+        if with_copies and self.render:
+            _lib.check(lib.ct_memcpy_async(self.pc_dev.data_ptr(), self.pc_host.data_ptr(), self.pc_host.numel() * 4, 1, st), 'H2D')
+        if self.render:
+            _lib.check(lib.ct_render_pre_hm(self.prm_dev.data_ptr(), self.cnt_dev.data_ptr(), self.max_blobs, det.B, H, W,
+                                            self.hm_in.data_ptr(), 1 if det.flip else 0, st), 'ct_render_pre_hm')
+        if det.flip and self.partial is None:
+            self.flip_slot(slot, st)
+        det.model._run_plan(self.plan, inputs=(cur, prev, self.hm_in), stem_partial=self.partial[slot] if self.partial else None)
+        if det.flip:
+            arr, n, pairs, h, w = self.flip_call
+            _lib.check(lib.ct_flip_merge(arr, n, pairs.ctypes.data, len(pairs), det.B, h, w, st), 'ct_flip_merge')
+        if getattr(det.opt, 'zero_tracking', False) and 'tracking' in self.merged:      # decode.py:142-143 `*= 0`
+            t = self.merged['tracking']
+            for b in range(t.shape[0]):
+                _lib.check(lib.ct_memset_async(t[b].data_ptr(), 0, t[b].numel() * 4, st), 'memset')
+        self.decoder.run()
+        if with_copies and not self.decoder.direct:
+            _lib.check(lib.ct_memcpy_async(self.host_out.data_ptr(), self.decoder.out.data_ptr(), self.host_out.numel() * 4, 2, st), 'D2H')
+            if HOST_FLAG:         # the native loop polls this flag instead of waiting in the runtime
+                _lib.check(lib.ct_signal_host(self.done_flag.data_ptr(), 1, st), 'ct_signal_host')
+
+    def capture(self):
+        """warm-up on a side stream, then one graph per slot: raw HIP graphs, or torch's under CENTERTRACK_RAW_GRAPH=0"""
+        try:
+            torch.cuda.synchronize()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.pre_stage(0)
+                self.device_frame(0)           # warm-up (lazy module loads must not happen in capture)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            # only C-ABI launches inside device_frame (no torch op, flip_test included): capture / replay
+            # straight through HIP
+            raw = os.environ.get('CENTERTRACK_RAW_GRAPH', '1') != '0'
+            for sl in range(self.nslots):
+                if raw:
+                    g = _HipGraph(lambda: self.device_frame(sl, True), collect=(sl == 0))      # (garbage is collected once, ahead of the first capture)
+                else:
+                    g = torch.cuda.CUDAGraph()
+                    with _lib.capture_guard(collect=False), torch.cuda.graph(g):
+                        self.device_frame(sl)
+                self.graphs[sl] = g
+            self.raw = raw
+        except Exception as e:
+            # never degrade silently: the eager launches are the same kernels at a fraction of the frame rate
+            if os.environ.get('CENTERTRACK_GRAPH_FALLBACK', '0') != '1':
+                raise _lib.CTError('HIP graph capture of the frame failed (%s); pass use_graph=False or set '
+                                   'CENTERTRACK_GRAPH_FALLBACK=1 to run eager launches' % (e,))
+            import warnings
+            warnings.warn('centertrack_amd: HIP graph capture failed (%s); using eager launches' % (e,))
+            self.graphs = [None] * self.nslots
+            torch.cuda.synchronize()
+        self.graph = self.graphs[0]
+
+    def make_loop(self):
+        """the native frame loop (ct_frame_loop_*, csrc/frame_loop.hip) over this context's graphs / buffers / trackers"""
+        det, lib, (H, W) = self.det, _lib.load(), self.hw
+        B, K, F = self.decoder.out.shape
+        d = _lib.FrameLoopDesc()
+        d.B, d.K, d.F = int(B), int(K), int(F)
+        self.loop_trackers = (ctypes.c_void_p * det.B)(*[f.h for f in det.fast])
+        d.trackers = ctypes.cast(self.loop_trackers, ctypes.POINTER(ctypes.c_void_p))
+        d.layout = self.row_layout
+        d.out_thresh, d.pre_thresh = float(det.opt.out_thresh), float(det.opt.pre_thresh)
+        d.inp_w, d.inp_h = int(W), int(H)
+        d.host_rows = self.host_out.data_ptr()
+        self.rows_keep = np.zeros(tuple(self.decoder.out.shape), np.float32)
+        d.rows_keep = self.rows_keep.ctypes.data
+        if self.render:
+            d.blob_params, d.blob_counts, d.blob_cap = self.prm_host.data_ptr(), self.cnt_host.data_ptr(), self.max_blobs
+        d.nslots = self.nslots
+        for i in range(self.nslots):
+            d.graphs[i], d.frames[i] = self.graphs[i].exec, self.frames[i].data_ptr()
+        d.frame_bytes = det.B * 3 * H * W * 4
+        self.loop_stream = torch.cuda.current_stream()
+        d.stream = self.loop_stream.cuda_stream
+        if self.partial is not None:
+            P = det.model._prepare()
+            d.pre.enabled = 1
+            d.pre.N, d.pre.H, d.pre.W = self.NB, int(H), int(W)
+            d.pre.w_x, d.pre.w_img = P['stem_w'][0].data_ptr(), P['stem_w'][1].data_ptr()
+            d.pre.scale3, d.pre.shift3 = P['stem_scale'].data_ptr(), P['stem_shift'].data_ptr()
+            for i in range(self.nslots):
+                d.pre.partial[i] = self.partial[i].ptr
+            d.pre.ldp = self.partial[0].ld
+            d.pre.flip_B = det.B if det.flip else 0
+        self.res_cap = det.fast[0].cap
+        self.res_buf = np.zeros((det.B, self.res_cap), fast_track.TRACK_DTYPE)
+        d.results, d.results_cap = self.res_buf.ctypes.data, self.res_cap
+        d.done_flag = self.done_flag.data_ptr() if HOST_FLAG else None
+        h = lib.ct_frame_loop_create(ctypes.byref(d))
+        if not h:
+            raise _lib.CTError('ct_frame_loop_create: %s' % lib.ct_last_error().decode())
+        self.loop, self.loop_desc = ctypes.c_void_p(h), d
+        self.counts = np.zeros(det.B, np.int32)
+        self.tin, self.tinv = np.zeros((det.B, 6), np.float64), np.zeros((det.B, 6), np.float32)
+        self.args = [_lib.FrameStepArgs(), _lib.FrameStepArgs()]
+        for a in self.args:
+            a.trans_input, a.trans_inv = self.tin.ctypes.data, self.tinv.ctypes.data
+
+    def forget_upload(self, uploaded):
+        """THE ordering rule of the frame slots, called from one place per frame path: a frame uploaded ahead (``uploaded``:
+        its record, or None) that is not used as it stands is forgotten before anything else writes the slot it targeted"""
+        if uploaded is not None and self.loop is not None:
+            _lib.load().ct_frame_loop_forget_upload(self.loop)
+        if uploaded is not None and self.copy_stream is not None:
+            self.copy_stream.synchronize()
+
+    def close(self):
+        """wait for the device and destroy the native loop: the one place that does"""
+        if self.loop is not None:
+            torch.cuda.synchronize()
+            _lib.load().ct_frame_loop_destroy(self.loop)      # (joins its helper threads)
+            self.loop = None
 
 
 class StreamDetector(object):
@@ -172,7 +456,7 @@ class StreamDetector(object):
                                             public_det=getattr(opt, 'public_det', False))
                      for _ in range(self.B)] if self.native else None
         self._last_dets = None
-        self._prefetched = None    # (host tensor, its _version, event) of a frame uploaded ahead by step(prefetch=...)
+        self._prefetched = None    # (host tensor, its _version, slot) of a frame uploaded ahead by step(prefetch=...)
         self.started = [False] * self.B
         # device-side pre-processing of raw u8 frames (ct_preprocess_device): normalisation table + staging buffers
         lut = np.empty((3, 256), np.float32)
@@ -192,237 +476,29 @@ class StreamDetector(object):
     def __del__(self):
         try:
             ctx = self._ctx
-            if ctx is not None and ctx.get('loop') is not None:
+            if ctx is not None and ctx.loop is not None:
                 # (collected while the current stream is capturing -- somebody else's graph: waiting for the device here would
                 #  invalidate that capture; the native loop is leaked instead.  The package's own captures keep the collector
                 #  out altogether, _lib.capture_guard)
                 if os.environ.get('CT_NO_CAPTURE_GUARD') != '1' and torch.cuda.is_current_stream_capturing():
                     return
-                torch.cuda.synchronize()
-                _lib.load().ct_frame_loop_destroy(ctx['loop'])      # (joins its helper threads)
-                ctx['loop'] = None
+                ctx.close()
         except Exception:
             pass
 
     # ---- per-shape device context (static buffers + captured graph) ----------------------
     def _context(self, H, W):
-        if self._ctx is not None and self._ctx['hw'] == (H, W):
+        if self._ctx is not None and self._ctx.hw == (H, W):
             return self._ctx
-        if self._ctx is not None and self._ctx.get('loop') is not None:      # another input size: a new loop below
-            torch.cuda.synchronize()
-            _lib.load().ct_frame_loop_destroy(self._ctx['loop'])
-            self._ctx['loop'] = None
-        opt = self.opt
-        NB = self.B * (2 if self.flip else 1)
-        with_img = bool(getattr(opt, 'tracking', False)) and bool(getattr(opt, 'pre_img', True))
-        with_hm = bool(getattr(opt, 'tracking', False)) and bool(getattr(opt, 'pre_hm', False))
-        plan = self.model.get_plan(NB, H, W, with_img, with_hm, True, self.sparse)
-        x_in, img_in, hm_in = plan['inputs']
-        outs = plan['outputs']
-        ctx = {'hw': (H, W), 'plan': plan, 'NB': NB}
-        if self.flip:
-            # detector.py:311-332: averaged heads get a merged [B,c,h,w] map (ct_flip_merge, one launch for all of
-            # them); the heads the reference takes from the un-flipped image alone are read in place (first B images)
-            modes = {'hps': _lib.CT_FLIP_JOINT_OFFSETS, 'hm_hp': _lib.CT_FLIP_JOINTS}
-            modes.update({k: _lib.CT_FLIP_AVG for k in AVERAGE_FLIPS})
-            modes.update({k: _lib.CT_FLIP_NEG_EVEN for k in NEG_AVERAGE_FLIPS})
-            merged, fl = {}, []
-            for k, v in outs.items():
-                if k in modes:
-                    merged[k] = torch.empty((self.B,) + tuple(v.shape[1:]), device=self.device)
-                    fl.append((v, merged[k], modes[k]))
-                else:
-                    merged[k] = v[:self.B]
-            heads_arr = (_lib.FlipHead * len(fl))()
-            for i, (v, m, mode) in enumerate(fl):
-                assert v.stride(3) == 1 and v.stride(2) == v.shape[3] and v.stride(1) == v.shape[2] * v.shape[3]
-                heads_arr[i].src, heads_arr[i].dst = v.data_ptr(), m.data_ptr()
-                heads_arr[i].src_batch_stride, heads_arr[i].C, heads_arr[i].mode = v.stride(0), v.shape[1], mode
-            pairs = np.ascontiguousarray(getattr(opt, 'flip_idx', COCO_FLIP_IDX), np.int32).reshape(-1, 2)
-            hm0 = outs['hm']
-            ctx['flip_call'] = (heads_arr, len(fl), pairs, int(hm0.shape[2]), int(hm0.shape[3]))
-        else:
-            merged = outs
-        ctx['merged'] = merged
-        dec_heads = {k: v for k, v in merged.items() if k != 'hm'}
-        ctx['done_flag'] = torch.zeros((16,), dtype=torch.int32).pin_memory()      # (its own cache line)
-        sparse = plan.get('sparse')
-        if sparse is not None:
-            sparse = dict(sparse, zero_tracking=bool(getattr(opt, 'zero_tracking', False)), flip=self.flip)
-        F = ops.Decoder.row_floats(dec_heads, [n for n, *_ in sparse['heads']] if sparse else None)
-        ctx['host_out'] = torch.zeros((merged['hm'].shape[0], opt.K, F), dtype=torch.float32).pin_memory()
-        # (round 3: the decode stores its rows straight into the pinned block and raises the end-of-frame flag itself --
-        #  no D2H copy node and no flag kernel at the end of the frame graph; not with pose heads, whose kernels
-        #  complete the rows after the decode)
-        direct = HOST_FLAG and HOST_ROWS
-        ctx['decoder'] = ops.Decoder(merged['hm'], dec_heads, opt.K, host_out=ctx['host_out'] if direct else None,
-                                     done_flag=ctx['done_flag'] if direct else None, sparse=sparse)
-        assert tuple(ctx['decoder'].out.shape) == tuple(ctx['host_out'].shape)
-        ctx['host_rows'] = ctx['host_out'].numpy()
-        ctx['host_hm'] = torch.zeros((NB, 1, H, W), dtype=torch.float32).pin_memory() if (with_hm and not self.native) else None
-        render = self.native and with_hm
-        if render:
-            # blob triples of every stream followed by the per-stream counts: ONE pinned buffer, one H2D per frame
-            nblob = ctx['max_blobs'] = fast_track.max_blobs(opt.K)
-            nprm = self.B * nblob * 3
-            ctx['pc_host'] = torch.zeros((nprm + self.B,), dtype=torch.int32).pin_memory()
-            ctx['pc_dev'] = torch.zeros((nprm + self.B,), dtype=torch.int32, device=self.device)
-            ctx['prm_host'] = ctx['pc_host'][:nprm].view(self.B, nblob, 3)
-            ctx['cnt_host'] = ctx['pc_host'][nprm:]
-            ctx['prm_dev'] = ctx['pc_dev'][:nprm]
-            ctx['cnt_dev'] = ctx['pc_dev'][nprm:]
-        if self.native:
-            ctx['row_layout'] = fast_track.row_layout(ctx['decoder'].layout)
-        # Frame buffers owned by THIS detector (the plan's activation buffers are shared by every detector of
-        # the model).  They ROTATE: the frame of step t is written into slot t % nslots and read as `pre_img` from
-        # there at step t+1, so the reference's `self.pre_images = images` (detector.py:148) costs no copy; with three
-        # slots the frame of step t+1 can be uploaded straight into ITS slot while the graph of step t still reads
-        # slots t and t-1 (round 3: no staging buffer, no device-to-device copy between upload and launch); one
-        # captured graph per slot.
-        nslots = 3 if img_in is not None else 2
-        ctx['nslots'] = nslots
-        ctx['frames'] = [torch.zeros_like(x_in) for _ in range(nslots)]
-        ctx['slot'] = 0                    # slot of the NEXT frame
-        ctx['graphs'] = [None] * nslots
-        ctx['raw'] = False
-        ctx['loop'] = None
-        ctx['launched'] = None             # (frame tensor, version, metas) of a frame the native loop launched ahead
-        ctx['copy_stream'] = None
-        split = img_in is not None and hm_in is not None and 0 < NB <= SPLIT_STEM_MAX
-        ctx['partial'] = [ops.new_view(NB, H, W, 16, self.device) for _ in range(nslots)] if split else None
-
-        def pre_stage(slot):
-            """the part of a frame that does not depend on the tracker: the mirrored half of a flip_test batch and the
-            x / pre_img terms of the stem.  The native loop runs it for frame t+1 behind the graph of frame t."""
-            if not split:
-                return
-            cur, prev = ctx['frames'][slot], ctx['frames'][(slot - 1) % nslots]
-            if self.flip:
-                _lib.check(_lib.load().ct_flip_images(cur.data_ptr(), cur[self.B:].data_ptr(), self.B * 3 * H, W,
-                                                      _lib.stream_ptr()), 'ct_flip_images')
-            self.model.run_stem_partial(cur, prev, ctx['partial'][slot])
-        ctx['pre_stage'] = pre_stage
-
-        def device_frame(slot=0, with_copies=False):
-            """all device work of one frame; ``with_copies``: also the H2D of the prior-heat-map blobs and the D2H
-            of the packed detections (fixed pinned buffers), so that a captured frame is ONE graph launch"""
-            cur = ctx['frames'][slot]
-            prev = ctx['frames'][(slot - 1) % nslots] if img_in is not None else None
-            if with_copies and render:
-                _lib.check(_lib.load().ct_memcpy_async(ctx['pc_dev'].data_ptr(), ctx['pc_host'].data_ptr(),
-                                                       ctx['pc_host'].numel() * 4, 1, _lib.stream_ptr()), 'H2D')
-            lib = _lib.load()
-            if render:
-                _lib.check(lib.ct_render_pre_hm(ctx['prm_dev'].data_ptr(), ctx['cnt_dev'].data_ptr(),
-                                                ctx['max_blobs'], self.B, H, W, hm_in.data_ptr(),
-                                                1 if self.flip else 0, _lib.stream_ptr()), 'ct_render_pre_hm')
-            if self.flip and not split:
-                # the mirrored half of the batch (detector.py:224-226), built from the frames already in HBM
-                _lib.check(lib.ct_flip_images(cur.data_ptr(), cur[self.B:].data_ptr(), self.B * 3 * H, W,
-                                              _lib.stream_ptr()), 'ct_flip_images')
-            self.model._run_plan(plan, inputs=(cur, prev, hm_in), stem_partial=ctx['partial'][slot] if split else None)
-            if self.flip:
-                arr, n, pairs, h, w = ctx['flip_call']
-                _lib.check(lib.ct_flip_merge(arr, n, pairs.ctypes.data, len(pairs), self.B, h, w, _lib.stream_ptr()),
-                           'ct_flip_merge')
-            if getattr(opt, 'zero_tracking', False) and 'tracking' in merged:      # decode.py:142-143 `*= 0`
-                t = merged['tracking']
-                for b in range(t.shape[0]):
-                    _lib.check(lib.ct_memset_async(t[b].data_ptr(), 0, t[b].numel() * 4, _lib.stream_ptr()), 'memset')
-            ctx['decoder'].run()
-            if with_copies and not ctx['decoder'].direct:
-                _lib.check(_lib.load().ct_memcpy_async(ctx['host_out'].data_ptr(), ctx['decoder'].out.data_ptr(),
-                                                       ctx['host_out'].numel() * 4, 2, _lib.stream_ptr()), 'D2H')
-                if HOST_FLAG:         # the native loop polls this flag instead of waiting in the runtime
-                    _lib.check(_lib.load().ct_signal_host(ctx['done_flag'].data_ptr(), 1, _lib.stream_ptr()), 'ct_signal_host')
-
-        ctx['device_frame'] = device_frame
+        if self._ctx is not None:
+            self._ctx.close()                                  # another input size: a new loop below
+        ctx = _FrameContext(self, H, W)
         if self.use_graph:
-            try:
-                torch.cuda.synchronize()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    pre_stage(0)
-                    device_frame(0)           # warm-up (lazy module loads must not happen in capture)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                # only C-ABI launches inside device_frame (no torch op, flip_test included): capture / replay
-                # straight through HIP
-                raw = os.environ.get('CENTERTRACK_RAW_GRAPH', '1') != '0'
-                for sl in range(nslots):
-                    if raw:
-                        g = _HipGraph(lambda: device_frame(sl, True), collect=(sl == 0))      # (garbage is collected once, ahead of the first capture)
-                    else:
-                        g = torch.cuda.CUDAGraph()
-                        with _lib.capture_guard(collect=False), torch.cuda.graph(g):
-                            device_frame(sl)
-                    ctx['graphs'][sl] = g
-                ctx['raw'] = raw
-            except Exception as e:
-                # never degrade silently: the eager launches are the same kernels at a fraction of the frame rate
-                if os.environ.get('CENTERTRACK_GRAPH_FALLBACK', '0') != '1':
-                    raise _lib.CTError('HIP graph capture of the frame failed (%s); pass use_graph=False or set '
-                                       'CENTERTRACK_GRAPH_FALLBACK=1 to run eager launches' % (e,))
-                import warnings
-                warnings.warn('centertrack_amd: HIP graph capture failed (%s); using eager launches' % (e,))
-                ctx['graphs'] = [None] * nslots
-                torch.cuda.synchronize()
-        ctx['graph'] = ctx['graphs'][0]
-        if ctx['raw'] and self.native and NATIVE_LOOP:
-            self._make_loop(ctx, H, W, render)
+            ctx.capture()
+        if ctx.raw and self.native and NATIVE_LOOP:
+            ctx.make_loop()
         self._ctx = ctx
         return ctx
-
-    def _make_loop(self, ctx, H, W, render):
-        """the native frame loop (ct_frame_loop_*, csrc/frame_loop.hip) over this context's graphs / buffers / trackers"""
-        lib = _lib.load()
-        B, K, F = ctx['decoder'].out.shape
-        d = _lib.FrameLoopDesc()
-        d.B, d.K, d.F = int(B), int(K), int(F)
-        ctx['loop_trackers'] = (ctypes.c_void_p * self.B)(*[f.h for f in self.fast])
-        d.trackers = ctypes.cast(ctx['loop_trackers'], ctypes.POINTER(ctypes.c_void_p))
-        d.layout = ctx['row_layout']
-        d.out_thresh, d.pre_thresh = float(self.opt.out_thresh), float(self.opt.pre_thresh)
-        d.inp_w, d.inp_h = int(W), int(H)
-        d.host_rows = ctx['host_out'].data_ptr()
-        ctx['rows_keep'] = np.zeros(tuple(ctx['decoder'].out.shape), np.float32)
-        d.rows_keep = ctx['rows_keep'].ctypes.data
-        if render:
-            d.blob_params, d.blob_counts = ctx['prm_host'].data_ptr(), ctx['cnt_host'].data_ptr()
-            d.blob_cap = ctx['max_blobs']
-        d.nslots = ctx['nslots']
-        for i in range(ctx['nslots']):
-            d.graphs[i] = ctx['graphs'][i].exec
-            d.frames[i] = ctx['frames'][i].data_ptr()
-        d.frame_bytes = self.B * 3 * H * W * 4
-        ctx['loop_stream'] = torch.cuda.current_stream()
-        d.stream = ctx['loop_stream'].cuda_stream
-        if ctx['partial'] is not None:
-            P = self.model._prepare()
-            d.pre.enabled = 1
-            d.pre.N, d.pre.H, d.pre.W = ctx['NB'], int(H), int(W)
-            d.pre.w_x, d.pre.w_img = P['stem_w'][0].data_ptr(), P['stem_w'][1].data_ptr()
-            d.pre.scale3, d.pre.shift3 = P['stem_scale'].data_ptr(), P['stem_shift'].data_ptr()
-            for i in range(ctx['nslots']):
-                d.pre.partial[i] = ctx['partial'][i].ptr
-            d.pre.ldp = ctx['partial'][0].ld
-            d.pre.flip_B = self.B if self.flip else 0
-        ctx['res_cap'] = self.fast[0].cap
-        ctx['res_buf'] = np.zeros((self.B, ctx['res_cap']), fast_track.TRACK_DTYPE)
-        d.results, d.results_cap = ctx['res_buf'].ctypes.data, ctx['res_cap']
-        d.done_flag = ctx['done_flag'].data_ptr() if HOST_FLAG else None
-        h = lib.ct_frame_loop_create(ctypes.byref(d))
-        if not h:
-            raise _lib.CTError('ct_frame_loop_create: %s' % lib.ct_last_error().decode())
-        ctx['loop'] = ctypes.c_void_p(h)
-        ctx['loop_desc'] = d
-        ctx['counts'] = np.zeros(self.B, np.int32)
-        ctx['tin'] = np.zeros((self.B, 6), np.float64)
-        ctx['tinv'] = np.zeros((self.B, 6), np.float32)
-        ctx['args'] = [_lib.FrameStepArgs(), _lib.FrameStepArgs()]
-        for a in ctx['args']:
-            a.trans_input, a.trans_inv = ctx['tin'].ctypes.data, ctx['tinv'].ctypes.data
 
     def _warp_frame(self, s, image, meta, frames, H, W):
         """upload the raw u8 frame of stream ``s`` and warp / normalise it into ``frames[s]`` (and the mirrored copy
@@ -464,6 +540,17 @@ class StreamDetector(object):
             m['_trans_inv'] = cached = (ident, tinv)
         return cached[1]
 
+    def _gather(self, ctx):
+        """the gather hook, called right behind this frame's launch; the event after which the rows have been read, if any"""
+        ev = self.gather_fn(ctx.decoder.out) if self.gather_fn is not None else None
+        return ev if isinstance(ev, torch.cuda.Event) else None
+
+    @staticmethod
+    def _fill_timers(timers, t0, t1, t2, post, track):
+        """the reference's timer keys (detector.py:162-165); decode and merge are part of ``net`` here"""
+        if timers is not None:
+            timers.update({'pre': t1 - t0, 'net': t2 - t1, 'dec': 0.0, 'post': post, 'merge': 0.0, 'track': track})
+
     def _checked_submit(self, ctx, rc, what):
         """a submit can fail AFTER its graph launch (upload of the next frame, its pre-stage; frame_loop.hip: "the frame
         itself is in flight"): drain that frame and forget the half-issued upload before raising, so that the next
@@ -473,20 +560,20 @@ class StreamDetector(object):
             return
         lib = _lib.load()
         msg = lib.ct_last_error().decode('utf-8', 'replace')
-        lib.ct_frame_loop_wait(ctx['loop'])
-        lib.ct_frame_loop_forget_upload(ctx['loop'])
-        ctx['launched'] = None
+        lib.ct_frame_loop_wait(ctx.loop)
+        lib.ct_frame_loop_forget_upload(ctx.loop)
+        ctx.launched = None
         self._prefetched = None
         raise _lib.CTError('%s failed (%d): %s' % (what, rc, msg))
 
     def _drop_launched(self, ctx):
         """a frame the native loop launched ahead will not be used (other frame handed over, reset): wait for it and
         give its slot back -- the trackers never saw it"""
-        if ctx.get('loop') is not None and ctx['launched'] is not None:
-            _lib.check(_lib.load().ct_frame_loop_wait(ctx['loop']), 'ct_frame_loop_wait')
-            _lib.load().ct_frame_loop_forget_upload(ctx['loop'])      # (also: whatever was pre-staged is stale)
-            ctx['slot'] = (ctx['slot'] - 1) % ctx['nslots']
-            ctx['launched'] = None
+        if ctx.loop is not None and ctx.launched is not None:
+            _lib.check(_lib.load().ct_frame_loop_wait(ctx.loop), 'ct_frame_loop_wait')
+            _lib.load().ct_frame_loop_forget_upload(ctx.loop)      # (also: whatever was pre-staged is stale)
+            ctx.slot = (ctx.slot - 1) % ctx.nslots
+            ctx.launched = None
 
     def _step_native(self, ctx, images, metas, timers, prefetch, prefetch_metas):
         """steady state of the native tracking path: the frame loop of csrc/frame_loop.hip.  With ``prefetch`` AND
@@ -498,7 +585,7 @@ class StreamDetector(object):
         torch-side work of the step (slot copy, gather hook) is issued on the loop stream, and the caller's stream
         waits for the loop stream on the way out."""
         cs = torch.cuda.current_stream()
-        ls = ctx['loop_stream']
+        ls = ctx.loop_stream
         if cs != ls:
             ls.wait_stream(cs)
             try:
@@ -508,47 +595,53 @@ class StreamDetector(object):
                 cs.wait_stream(ls)
         return self._step_native_on_loop_stream(ctx, images, metas, timers, prefetch, prefetch_metas)
 
+    def _native_stage_frame(self, ctx, cur, slot, images, metas):
+        """the transforms of this frame's metas and where the loop finds the frame (``cur``: its FrameStepArgs)"""
+        for s_ in range(self.B):
+            ctx.tinv[s_] = self._meta_transforms(metas[s_]).reshape(-1)
+            ctx.tin[s_] = np.asarray(metas[s_]['trans_input'], np.float64).reshape(-1)
+        uploaded, self._prefetched = self._prefetched, None
+        cur.slot, cur.frame, cur.next_frame = slot, None, None
+        cur.frame_kind = _frame_source(images, uploaded, slot)
+        if cur.frame_kind != _lib.CT_FRAME_UPLOADED:
+            ctx.forget_upload(uploaded)            # (a stale upload may still target this slot: drained BEFORE the copy)
+        if cur.frame_kind in (_lib.CT_FRAME_DEVICE, _lib.CT_FRAME_HOST):
+            cur.frame = images.data_ptr()
+        elif cur.frame_kind == _lib.CT_FRAME_IN_PLACE:
+            ctx.frames[slot][:self.B].copy_(images)
+
+    def _native_results(self, ctx):
+        """the track records the loop left per stream, copied: the loop rewrites its block with the next frame"""
+        out = []
+        for s_ in range(self.B):
+            k = int(ctx.counts[s_])
+            if k > ctx.res_cap:                                # (max_age > 0 lets the track list grow: re-read it)
+                tmp = np.zeros(k, fast_track.TRACK_DTYPE)
+                got = _lib.load().ct_tracker_get_tracks(self.fast[s_].h, tmp.ctypes.data, k)
+                out.append(tmp[:min(got, k)])
+            else:
+                out.append(ctx.res_buf[s_, :k].copy())
+        return out
+
     def _step_native_on_loop_stream(self, ctx, images, metas, timers, prefetch, prefetch_metas):
         lib = _lib.load()
         t0 = time.time()
-        B, n = self.B, ctx['nslots']
-        loop = ctx['loop']
-        launched = ctx['launched']
+        n, loop = ctx.nslots, ctx.loop
+        launched = ctx.launched
         ahead = launched is not None and launched[0] is images and launched[1] == images._version
         if launched is not None and not ahead:
             self._drop_launched(ctx)
-        cur, nxt = ctx['args']
+        cur, nxt = ctx.args
         if ahead:
             # this frame is already in flight; its prior heat-map was built with the metas promised last step
             if any(a is not b for a, b in zip(launched[2], metas)) and [self._meta_transforms(m).tobytes() for m in metas] != launched[3]:
                 raise _lib.CTError('step(): the metas of this frame differ from the prefetch_metas promised for it')
-            ctx['launched'] = None
-            slot = (ctx['slot'] - 1) % n
+            ctx.launched = None
+            slot = (ctx.slot - 1) % n
         else:
-            slot = ctx['slot']
-            tin, tinv = ctx['tin'], ctx['tinv']
-            for s_ in range(B):
-                tinv[s_] = self._meta_transforms(metas[s_]).reshape(-1)
-                tin[s_] = np.asarray(metas[s_]['trans_input'], np.float64).reshape(-1)
-            pf = self._prefetched
-            self._prefetched = None
-            cur.slot, cur.frame, cur.next_frame = slot, None, None
-            if pf is not None and pf[0] is images and pf[1] == images._version and pf[2] == slot:
-                cur.frame_kind = _lib.CT_FRAME_UPLOADED
-            elif images.dtype == torch.float32 and images.is_contiguous():
-                cur.frame_kind = _lib.CT_FRAME_DEVICE if images.device.type == 'cuda' else _lib.CT_FRAME_HOST
-                cur.frame = images.data_ptr()
-            else:
-                if pf is not None:        # a stale prefetch upload may still target this slot: drain it BEFORE the copy
-                    lib.ct_frame_loop_forget_upload(loop)
-                    pf = None
-                ctx['frames'][slot][:B].copy_(images)
-                cur.frame_kind = _lib.CT_FRAME_IN_PLACE
-            if pf is not None and cur.frame_kind != _lib.CT_FRAME_UPLOADED:
-                lib.ct_frame_loop_forget_upload(loop)
-        can_prefetch = (prefetch is not None and torch.is_tensor(prefetch) and prefetch.device.type == 'cpu'
-                        and prefetch.dtype == torch.float32 and prefetch.is_contiguous()
-                        and tuple(prefetch.shape) == tuple(images.shape))
+            slot = ctx.slot
+            self._native_stage_frame(ctx, cur, slot, images, metas)
+        can_prefetch = _prefetchable(prefetch, images.shape)
         t1 = time.time()
         if ahead:
             if can_prefetch:            # the frame after the one in flight: its slot was last read by the finished frame
@@ -557,48 +650,34 @@ class StreamDetector(object):
             if can_prefetch:
                 cur.next_frame = prefetch.data_ptr()
             if self._rows_free is not None:                    # (left by a step of the Python path)
-                ctx['loop_stream'].wait_event(self._rows_free)
+                ctx.loop_stream.wait_event(self._rows_free)
                 self._rows_free = None
             self._checked_submit(ctx, lib.ct_frame_loop_submit(loop, ctypes.byref(cur)), 'ct_frame_loop_submit')
-            ctx['slot'] = (slot + 1) % n
+            ctx.slot = (slot + 1) % n
         if can_prefetch:
             self._prefetched = (prefetch, prefetch._version, (slot + 1) % n)
-        if self.gather_fn is not None:
-            # (the hook enqueues its reader of the device rows behind this frame's graph; the event it returns is waited
-            # for ON THE STREAM right here, i.e. between this graph and the next one, whoever launches that)
-            ev = self.gather_fn(ctx['decoder'].out)
-            if isinstance(ev, torch.cuda.Event):
-                ctx['loop_stream'].wait_event(ev)
-        counts = ctx['counts']
-        early = (can_prefetch and prefetch_metas is not None
-                 and all(a is b for a, b in zip(prefetch_metas, metas)))
+        # (the hook enqueues its reader of the device rows behind this frame's graph; the event it returns is waited
+        # for ON THE STREAM right here, i.e. between this graph and the next one, whoever launches that)
+        ev = self._gather(ctx)
+        if ev is not None:
+            ctx.loop_stream.wait_event(ev)
+        counts = ctx.counts
+        early = can_prefetch and prefetch_metas is not None and all(a is b for a, b in zip(prefetch_metas, metas))
         if early:
             # finish this frame and launch the next one in ONE native call: the GPU idles for the association only
             nxt.slot, nxt.frame_kind, nxt.frame, nxt.next_frame = (slot + 1) % n, _lib.CT_FRAME_UPLOADED, None, None
-            ctx['slot'] = (slot + 1) % n            # (where the loop stands if the call below fails half-way)
+            ctx.slot = (slot + 1) % n            # (where the loop stands if the call below fails half-way)
             self._checked_submit(ctx, lib.ct_frame_loop_finish_submit(loop, ctypes.byref(cur), counts.ctypes.data,
                                                                       ctypes.byref(nxt)), 'ct_frame_loop_finish_submit')
-            ctx['slot'] = (slot + 2) % n
-            ctx['launched'] = (prefetch, prefetch._version, list(metas),
-                               [self._meta_transforms(m).tobytes() for m in metas])
+            ctx.slot = (slot + 2) % n
+            ctx.launched = (prefetch, prefetch._version, list(metas), [self._meta_transforms(m).tobytes() for m in metas])
             self._prefetched = None
         else:
             _lib.check(lib.ct_frame_loop_finish(loop, ctypes.byref(cur), counts.ctypes.data), 'ct_frame_loop_finish')
         t2 = time.time()
         self._last_dets = None
-        res, cap = ctx['res_buf'], ctx['res_cap']
-        out = []
-        for s_ in range(B):
-            k = int(counts[s_])
-            if k > cap:                                        # (max_age > 0 lets the track list grow: re-read it)
-                tmp = np.zeros(k, fast_track.TRACK_DTYPE)
-                got = lib.ct_tracker_get_tracks(self.fast[s_].h, tmp.ctypes.data, k)
-                out.append(tmp[:min(got, k)])
-            else:
-                out.append(res[s_, :k].copy())
-        if timers is not None:
-            timers.update({'pre': t1 - t0, 'net': t2 - t1, 'dec': 0.0, 'post': 0.0, 'merge': 0.0,
-                           'track': time.time() - t2})
+        out = self._native_results(ctx)
+        self._fill_timers(timers, t0, t1, t2, 0.0, time.time() - t2)
         return out
 
     def step(self, images, metas, timers=None, prefetch=None, prefetch_metas=None):
@@ -626,9 +705,7 @@ class StreamDetector(object):
         else:
             H, W = int(images.shape[2]), int(images.shape[3])
         ctx = self._context(H, W)
-        x_in, img_in, hm_in = ctx['plan']['inputs']
-        lib = _lib.load()
-        if (ctx['loop'] is not None and not raw_frames and all(self.started) and tuple(images.shape) == (B, 3, H, W)
+        if (ctx.loop is not None and not raw_frames and all(self.started) and tuple(images.shape) == (B, 3, H, W)
                 and not getattr(opt, 'public_det', False) and not getattr(opt, 'zero_tracking', False)):
             return self._step_native(ctx, images, metas, timers, prefetch, prefetch_metas)
         self._drop_launched(ctx)
@@ -636,134 +713,148 @@ class StreamDetector(object):
         # frame: looked up once per step)
         cur = torch.cuda.current_stream()
         sp = ctypes.c_void_p(cur.cuda_stream)
-        n = ctx['nslots']
-        slot = ctx['slot']
-        fr = ctx['frames'][slot]
-        pf = self._prefetched
-        self._prefetched = None                                # (a frame uploaded ahead serves the very next call only)
-        # ---- the frame goes straight into its rotation slot (images [0, B); the mirrored images [B, 2B) of
-        #      flip_test are built on the device by the frame's first launch, detector.py:224-226) ----
-        if raw_frames:
-            self._forget_upload(ctx, pf)
-            for s in range(B):
-                self._warp_frame(s, images[s], metas[s], fr, H, W)
+        slot = ctx.slot
+        self._stage_frame(ctx, slot, images, metas, cur, sp)
+        if bool(getattr(opt, 'tracking', False)):
+            self._start_streams(ctx, slot, metas, sp)
+            self._prior_heat_map(ctx, metas)
+            self.started[:] = [True] * B                       # (only now: the heat map raises on a broken meta)
+        t1 = time.time()
+        self._launch(ctx, slot, cur, sp)
+        self._prefetch_next(ctx, slot, prefetch)
+        self._rows_free = self._gather(ctx)
+        if ctx.raw:                                            # (the D2H of the rows is the graph's last node)
+            _lib.check(_lib.load().ct_stream_synchronize(sp), 'ct_stream_synchronize')
         else:
+            ctx.host_out.copy_(ctx.decoder.out, non_blocking=True)
+            cur.synchronize()
+        t2 = time.time()
+        if ctx.rows_keep is not None:
+            ctx.rows_keep[...] = ctx.host_rows                 # (last_dets reads the kept copy when a native loop exists)
+        self._last_dets = None                                 # unpacked on demand (last_dets)
+        results, t_post, t_track = self._associate(ctx, ctx.host_rows, metas)
+        self._fill_timers(timers, t0, t1, t2, t_post, t_track)
+        return results
+
+    def _stage_frame(self, ctx, slot, images, metas, cur, sp):
+        """``pre_process`` of raw frames on the device (detector.py:80-82, 218-226) or ``images.to(device)``
+        (detector.py:93-94): the frame goes straight into its rotation slot (images [0, B); the mirrored images [B, 2B) of
+        flip_test are built on the device by the frame's first launch, detector.py:224-226)"""
+        B, (H, W), fr = self.B, ctx.hw, ctx.frames[slot]
+        uploaded, self._prefetched = self._prefetched, None    # (a frame uploaded ahead serves the very next call only)
+        source = None                                          # (raw frames)
+        if not isinstance(images, (list, tuple)):
             if tuple(images.shape) != (B, 3, H, W):
                 raise _lib.CTError('step() expects [%d,3,%d,%d] frames, got %s' % (B, H, W, tuple(images.shape)))
-            # the SAME tensor object, unmodified since it was handed over (an in-place edit bumps ``_version``; a new
-            # tensor at a recycled address is another object), uploaded into THIS slot
-            if pf is not None and pf[0] is images and pf[1] == images._version and pf[2] == slot:
-                if ctx['loop'] is not None:
-                    self._forget_upload(ctx, pf)                   # (uploaded by the native loop's copy stream: wait on the host; rare path)
-                else:
-                    cur.wait_event(ctx['frame_ready'])             # uploaded by the previous step's ``prefetch``
+            source = _frame_source(images, uploaded, slot)
+        if source == _lib.CT_FRAME_UPLOADED and ctx.loop is None:
+            cur.wait_event(ctx.frame_ready)                    # uploaded by the previous step's ``prefetch``
+        else:                     # (also THIS frame if the native loop's copy stream uploaded it: a wait on the host; rare path)
+            ctx.forget_upload(uploaded)
+        if source is None:
+            for s in range(B):
+                self._warp_frame(s, images[s], metas[s], fr, H, W)
+        elif source in (_lib.CT_FRAME_HOST, _lib.CT_FRAME_DEVICE):
+            # one DMA from wherever the caller keeps the frame: H2D for a host tensor (detector.py:93-94 -- pinned
+            # memory makes it asynchronous), D2D for a resident one
+            _lib.check(_lib.load().ct_memcpy_async(fr.data_ptr(), images.data_ptr(), images.numel() * 4,
+                                                   1 if source == _lib.CT_FRAME_HOST else 0, sp), 'frame copy')
+        elif source == _lib.CT_FRAME_IN_PLACE:
+            fr[:B].copy_(images)
+
+    def _start_streams(self, ctx, slot, metas, sp):
+        """first frame of a stream (detector.py:97-103): ``pre_dets`` into its tracker, ``pre_images = images``"""
+        B = self.B
+        fresh = [s for s in range(B) if not self.started[s]]
+        for s in fresh:
+            pre_dets = metas[s].get('pre_dets', [])
+            if self.native and len(pre_dets) > 0:
+                self.fast[s].init_tracks(pre_dets)             # tracker.init_track, detector.py:101-102
+            if not self.native:
+                self.trackers[s].init_track(pre_dets)
+        if ctx.img_in is not None:
+            # first frame of a stream: pre_images = images (detector.py:99-103)
+            fr, prev = ctx.frames[slot], ctx.frames[(slot - 1) % ctx.nslots]
+            if fresh and self.flip:
+                ctx.flip_slot(slot, sp)
+            if len(fresh) == B:
+                prev.copy_(fr)
             else:
-                self._forget_upload(ctx, pf)
-                if images.dtype == torch.float32 and images.is_contiguous():
-                    # one DMA from wherever the caller keeps the frame: H2D for a host tensor (detector.py:93-94 -- pinned
-                    # memory makes it asynchronous), D2D for a resident one
-                    kind = 0 if images.device.type == 'cuda' else 1
-                    _lib.check(lib.ct_memcpy_async(fr.data_ptr(), images.data_ptr(), images.numel() * 4, kind, sp),
-                               'frame copy')
-                else:
-                    fr[:B].copy_(images)
-        tracking = bool(getattr(opt, 'tracking', False))
-        if tracking:
-            for s in range(B):
-                if not self.started[s]:                        # detector.py:97-103
-                    pre_dets = metas[s].get('pre_dets', [])
-                    if self.native and len(pre_dets) > 0:
-                        self.fast[s].init_tracks(pre_dets)         # tracker.init_track, detector.py:101-102
-                    if not self.native:
-                        self.trackers[s].init_track(pre_dets)
-            if img_in is not None:
-                # first frame of a stream: pre_images = images (detector.py:99-103)
-                prev = ctx['frames'][(slot - 1) % n]
-                fresh = [s for s in range(B) if not self.started[s]]
-                if fresh and self.flip:
-                    _lib.check(lib.ct_flip_images(fr.data_ptr(), fr[B:].data_ptr(), B * 3 * H, W, sp), 'ct_flip_images')
-                if len(fresh) == B:
-                    prev.copy_(fr)
-                else:
-                    for s in fresh:
-                        prev[s].copy_(fr[s])
-                        if self.flip:
-                            prev[B + s].copy_(fr[B + s])
-            if hm_in is not None and self.native:
-                ph, ch = ctx['prm_host'].numpy(), ctx['cnt_host'].numpy()
-                for s in range(B):
-                    m = metas[s]
-                    ch[s], _ = self.fast[s].prehm_params(opt.pre_thresh, m['trans_input'], m['inp_width'],
-                                                         m['inp_height'], out=ph[s])
-                if not ctx['raw']:                             # (the raw graph carries this copy itself)
-                    ctx['pc_dev'].copy_(ctx['pc_host'], non_blocking=True)
-            elif hm_in is not None:
-                hh = ctx['host_hm']
-                for s in range(B):
-                    render_pre_hm(self.trackers[s].tracks, metas[s], opt.pre_thresh, out=hh[s, 0].numpy(),
-                                  with_hm=not getattr(opt, 'zero_pre_hm', False))
+                for s in fresh:
+                    prev[s].copy_(fr[s])
                     if self.flip:
-                        hh[B + s, 0].copy_(torch.flip(hh[s, 0], [1]))
-                hm_in.copy_(hh, non_blocking=True)
+                        prev[B + s].copy_(fr[B + s])
+
+    def _prior_heat_map(self, ctx, metas):
+        """``_get_additional_inputs`` (detector.py:104-110, 254-290): the blobs of the native trackers, which the frame
+        renders on the device, or ``render_pre_hm`` on the host and one H2D"""
+        opt, B = self.opt, self.B
+        if ctx.hm_in is not None and self.native:
+            ph, ch = ctx.prm_host.numpy(), ctx.cnt_host.numpy()
             for s in range(B):
-                self.started[s] = True
-        t1 = time.time()
+                m = metas[s]
+                ch[s], _ = self.fast[s].prehm_params(opt.pre_thresh, m['trans_input'], m['inp_width'], m['inp_height'], out=ph[s])
+            if not ctx.raw:                                    # (the raw graph carries this copy itself)
+                ctx.pc_dev.copy_(ctx.pc_host, non_blocking=True)
+        elif ctx.hm_in is not None:
+            hh = ctx.host_hm
+            for s in range(B):
+                render_pre_hm(self.trackers[s].tracks, metas[s], opt.pre_thresh, out=hh[s, 0].numpy(),
+                              with_hm=not getattr(opt, 'zero_pre_hm', False))
+                if self.flip:
+                    hh[B + s, 0].copy_(torch.flip(hh[s, 0], [1]))
+            ctx.hm_in.copy_(hh, non_blocking=True)
+
+    def _launch(self, ctx, slot, cur, sp):
+        """``process`` (detector.py:118-119, 300-350): the pre-stage unless it ran ahead, then the frame as a raw graph,
+        a torch graph or eager launches"""
         if self._rows_free is not None:                        # (a side-stream reader of the previous frame's rows)
             cur.wait_event(self._rows_free)
             self._rows_free = None
-        if ctx['partial'] is not None:                         # the tracker-independent part (unless it ran ahead)
-            if ctx['loop'] is not None:
-                _lib.check(lib.ct_frame_loop_prestage(ctx['loop'], slot), 'ct_frame_loop_prestage')
+        if ctx.partial is not None:                            # the tracker-independent part (unless it ran ahead)
+            if ctx.loop is not None:
+                _lib.check(_lib.load().ct_frame_loop_prestage(ctx.loop, slot), 'ct_frame_loop_prestage')
             else:
-                ctx['pre_stage'](slot)
-        if ctx['raw']:
-            ctx['graphs'][slot].replay(sp)
-        elif ctx['graphs'][slot] is not None:
-            ctx['graphs'][slot].replay()
+                ctx.pre_stage(slot)
+        if ctx.raw:
+            ctx.graphs[slot].replay(sp)
+        elif ctx.graphs[slot] is not None:
+            ctx.graphs[slot].replay()
         else:
-            ctx['device_frame'](slot)
-        ctx['slot'] = (slot + 1) % n                           # this frame is the next step's pre_img
-        if (prefetch is not None and torch.is_tensor(prefetch) and prefetch.device.type == 'cpu'
-                and prefetch.dtype == torch.float32 and prefetch.is_contiguous() and tuple(prefetch.shape) == (B, 3, H, W)):
-            # straight into the NEXT frame's slot: it was last read (as pre_img) by the previous frame's graph, which the
-            # host has waited for -- the graph just launched reads this slot and the one before it only
-            ns = (slot + 1) % n
-            if ctx['loop'] is not None:                        # (the next step may be the native loop's: its copy stream)
-                _lib.check(lib.ct_frame_loop_upload(ctx['loop'], ns, prefetch.data_ptr()), 'ct_frame_loop_upload')
-            else:
-                if ctx['copy_stream'] is None:
-                    ctx['copy_stream'] = torch.cuda.Stream(device=self.device)
-                    ctx['frame_ready'] = torch.cuda.Event()
-                    ctx['copy_sp'] = ctypes.c_void_p(ctx['copy_stream'].cuda_stream)
-                _lib.check(lib.ct_memcpy_async(ctx['frames'][ns].data_ptr(), prefetch.data_ptr(), prefetch.numel() * 4, 1,
-                                               ctx['copy_sp']), 'prefetch')
-                ctx['frame_ready'].record(ctx['copy_stream'])
-            self._prefetched = (prefetch, prefetch._version, ns)
-        if self.gather_fn is not None:
-            ev = self.gather_fn(ctx['decoder'].out)
-            self._rows_free = ev if isinstance(ev, torch.cuda.Event) else None
-        if ctx['raw']:                                         # (the D2H of the rows is the graph's last node)
-            _lib.check(lib.ct_stream_synchronize(sp), 'ct_stream_synchronize')
+            ctx.device_frame(slot)
+        ctx.slot = (slot + 1) % ctx.nslots                     # this frame is the next step's pre_img (detector.py:148)
+
+    def _prefetch_next(self, ctx, slot, prefetch):
+        """the next frame's ``images.to(device, non_blocking=True)`` (test.py:74-76, detector.py:93-94), one step early"""
+        if not _prefetchable(prefetch, (self.B, 3) + ctx.hw):
+            return
+        # straight into the NEXT frame's slot: it was last read (as pre_img) by the previous frame's graph, which the
+        # host has waited for -- the graph just launched reads this slot and the one before it only
+        lib, ns = _lib.load(), (slot + 1) % ctx.nslots
+        if ctx.loop is not None:                               # (the next step may be the native loop's: its copy stream)
+            _lib.check(lib.ct_frame_loop_upload(ctx.loop, ns, prefetch.data_ptr()), 'ct_frame_loop_upload')
         else:
-            ctx['host_out'].copy_(ctx['decoder'].out, non_blocking=True)
-            cur.synchronize()
-        t2 = time.time()
-        rows = ctx['host_rows']
-        if ctx.get('rows_keep') is not None:
-            ctx['rows_keep'][...] = rows                       # (last_dets reads the kept copy when a native loop exists)
-        self._last_dets = None                                 # unpacked on demand (last_dets)
-        all_results = []
-        t_post = t_track = 0.0
+            ctx.own_copy_stream()
+            _lib.check(lib.ct_memcpy_async(ctx.frames[ns].data_ptr(), prefetch.data_ptr(), prefetch.numel() * 4, 1, ctx.copy_sp), 'prefetch')
+            ctx.frame_ready.record(ctx.copy_stream)
+        self._prefetched = (prefetch, prefetch._version, ns)
+
+    def _associate(self, ctx, rows, metas):
+        """``post_process`` + ``merge_outputs`` + ``tracker.step`` per stream (detector.py:126-147, 371-377).  Returns
+        the results and the seconds spent in post-processing and in association."""
+        opt, results = self.opt, []
         if self.native:
             ta = time.time()
-            for s in range(B):
+            for s in range(self.B):
                 m = metas[s]
                 tinv = self._meta_transforms(m)
                 pub = m['cur_dets'] if getattr(opt, 'public_det', False) else None       # detector.py:141-142
-                all_results.append(self.fast[s].step(rows[s], ctx['row_layout'], opt.out_thresh, tinv, pub).copy())
-            t_track = time.time() - ta
-        dets = None if self.native else self.last_dets
-        for s in (range(B) if not self.native else []):
+                results.append(self.fast[s].step(rows[s], ctx.row_layout, opt.out_thresh, tinv, pub).copy())
+            return results, 0.0, time.time() - ta
+        dets = self.last_dets
+        tracking = bool(getattr(opt, 'tracking', False))
+        t_post = t_track = 0.0
+        for s in range(self.B):
             ta = time.time()
             meta = metas[s]
             one = {k: v[s:s + 1] for k, v in dets.items()}
@@ -774,23 +865,10 @@ class StreamDetector(object):
             if tracking:
                 public_det = meta['cur_dets'] if getattr(opt, 'public_det', False) else None   # (KeyError like the reference)
                 res = self.trackers[s].step(res, public_det)
-            tc = time.time()
             t_post += tb - ta
-            t_track += tc - tb
-            all_results.append(res)
-        if timers is not None:
-            timers.update({'pre': t1 - t0, 'net': t2 - t1, 'dec': 0.0, 'post': t_post, 'merge': 0.0,
-                           'track': t_track})
-        return all_results
-
-    def _forget_upload(self, ctx, pf):
-        """a frame uploaded ahead is not the one handed over now: make sure its copy is not still writing a slot"""
-        if pf is None:
-            return
-        if ctx['loop'] is not None:
-            _lib.load().ct_frame_loop_forget_upload(ctx['loop'])
-        if ctx['copy_stream'] is not None:
-            ctx['copy_stream'].synchronize()
+            t_track += time.time() - tb
+            results.append(res)
+        return results, t_post, t_track
 
     @property
     def last_dets(self):
@@ -798,14 +876,14 @@ class StreamDetector(object):
         packed rows -- the pinned D2H buffer is overwritten by the next step, while the reference's
         ``.cpu().numpy()`` arrays (detector.py:349-350) stay valid for as long as a caller keeps the results"""
         if self._last_dets is None and self._ctx is not None:
-            keep = self._ctx.get('rows_keep')          # (the native loop may already be writing the next frame's rows)
-            self._last_dets = self._ctx['decoder'].unpack((keep if keep is not None else self._ctx['host_rows']).copy())
+            keep = self._ctx.rows_keep                 # (the native loop may already be writing the next frame's rows)
+            self._last_dets = self._ctx.decoder.unpack((keep if keep is not None else self._ctx.host_rows).copy())
         return self._last_dets
 
     def reset_tracking(self, stream=None):
         if self._ctx is not None:
             self._drop_launched(self._ctx)
-            self._forget_upload(self._ctx, self._prefetched)
+            self._ctx.forget_upload(self._prefetched)
         for s in (range(self.B) if stream is None else [stream]):
             self.trackers[s].reset()
             if self.fast is not None:
