@@ -234,6 +234,13 @@ class PoseDesc(ctypes.Structure):
                 ('box_ltrb_batch_stride', ctypes.c_size_t)]
 
 
+class PoseSparseDesc(ctypes.Structure):
+    _fields_ = [('base', PoseDesc), ('feat', ctypes.c_void_p), ('ldf', ctypes.c_int), ('flip_B', ctypes.c_int),
+                ('hps_w1', ctypes.c_void_p), ('hps_b1', ctypes.c_void_p), ('hps_w2', ctypes.c_void_p), ('hps_b2', ctypes.c_void_p),
+                ('off_w1', ctypes.c_void_p), ('off_b1', ctypes.c_void_p), ('off_w2', ctypes.c_void_p), ('off_b2', ctypes.c_void_p),
+                ('flip_pairs', ctypes.c_void_p), ('num_pairs', ctypes.c_int)]
+
+
 class FlipHead(ctypes.Structure):
     _fields_ = [('src', ctypes.c_void_p), ('dst', ctypes.c_void_p), ('src_batch_stride', ctypes.c_size_t),
                 ('C', ctypes.c_int), ('mode', ctypes.c_int)]
@@ -348,7 +355,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_stem_conv_forward', 'ct_stem_conv_backward', 'ct_stem_conv_backward_workspace_bytes', 'ct_stem_bn_relu_sum',
            'ct_maxpool2x2', 'ct_upsample_add', 'ct_nchw_to_nhwc', 'ct_nhwc_to_nchw',
            'ct_decode_row_floats', 'ct_decode_workspace_bytes', 'ct_decode', 'ct_decode_pose_workspace_bytes',
-           'ct_decode_pose', 'ct_render_pre_hm',
+           'ct_decode_pose', 'ct_decode_pose_sparse_workspace_bytes', 'ct_decode_pose_sparse', 'ct_render_pre_hm',
            'ct_tracker_create', 'ct_tracker_destroy', 'ct_tracker_reset', 'ct_tracker_num_tracks',
            'ct_tracker_id_count', 'ct_tracker_get_tracks', 'ct_tracker_step', 'ct_tracker_prehm_params', 'ct_linear_assignment', 'ct_tracker_set_mode', 'ct_tracker_init_tracks',
            'ct_tracker_step_public', 'ct_tracker_step_dets', 'ct_transform_points',
@@ -461,6 +468,8 @@ def load():
     lib.ct_decode_pose_workspace_bytes.restype = sz
     lib.ct_decode_pose_workspace_bytes.argtypes = [ctypes.POINTER(PoseDesc)]
     lib.ct_decode_pose.argtypes = [ctypes.POINTER(PoseDesc), p]
+    lib.ct_decode_pose_sparse_workspace_bytes.argtypes = [ctypes.POINTER(PoseSparseDesc), ctypes.POINTER(sz)]
+    lib.ct_decode_pose_sparse.argtypes = [ctypes.POINTER(PoseSparseDesc), p]
     lib.ct_render_pre_hm.argtypes = [p, p, i, i, i, i, p, i, p]
     lib.ct_tracker_create.restype = p
     lib.ct_tracker_create.argtypes = [ctypes.c_float, i]

@@ -55,6 +55,12 @@ struct ct_wino_off_layer {
     float *part;
 };
 int ct_wino_offsets_group(const ct_wino_off_layer *layers, int n, void *stream);
+// pose.hip, shared with sparse_pose.hip: argument check (compact != 0: no hps map), the joint heat-maps as a ct_decode
+// descriptor, and the match + score launches (chps / coff: compact head values instead of the hps / hp_offset maps)
+int ct_pose_check(const ct_pose_desc *d, const char *who, int compact);
+void ct_pose_joint_desc(const ct_pose_desc *d, ct_decode_desc *jd);
+int ct_pose_match(const ct_pose_desc *d, const float *jrows, const int64_t *jinds, float *sc, const float *chps, const float *coff,
+                  void *stream);
 
 // XCD-aware decode of the linear workgroup id into (cout block, pixel-tile index).  Workgroups are dealt to
 // the 8 XCDs round-robin (id % 8) and each XCD has its own 4 MB L2, so with `per` = coutBlocks / 8 > 0

@@ -27,6 +27,8 @@ struct PoseArgs {
     const long long *inds;    // [B,K]
     const float *hps;         // [B,2J,h,w]
     const float *off;         // [B,2,h,w] or nullptr
+    const float *chps;        // compact values instead of the two maps (ct_decode_pose_sparse): hps [B*K][2J] at the winners ...
+    const float *coff;        // ... and the offset head [B*J*K][2] at the joint peaks (nullptr with chps: +0.5)
     const float *jrows;       // [B*J,K,4]: score, cls, x0, y0 of the joint peaks
     const long long *jinds;   // [B*J,K]
     float *sc;                // [B,J,K] per-joint score term
@@ -47,7 +49,10 @@ __global__ __launch_bounds__(128) void pose_match_kernel(PoseArgs a)
         const float *jr = a.jrows + ((size_t)bj * a.K + c) * 4;
         const float s = jr[0];
         float x = jr[2], y = jr[3];
-        if (a.off) {
+        if (a.coff) {
+            x = x + a.coff[((size_t)bj * a.K + c) * 2];
+            y = y + a.coff[((size_t)bj * a.K + c) * 2 + 1];
+        } else if (a.off) {
             const long long ind = a.jinds[(size_t)bj * a.K + c];
             x = x + a.off[(size_t)b * a.off_bs + ind];
             y = y + a.off[(size_t)b * a.off_bs + a.HW + ind];
@@ -64,8 +69,12 @@ __global__ __launch_bounds__(128) void pose_match_kernel(PoseArgs a)
     for (int k = threadIdx.x; k < a.K; k += blockDim.x) {
         const float *row = a.rows + ((size_t)b * a.K + k) * a.F;
         const long long ind = a.inds[(size_t)b * a.K + k];
-        const float rx = a.hps[(size_t)b * a.hps_bs + (size_t)(2 * j) * a.HW + ind] + row[2];
-        const float ry = a.hps[(size_t)b * a.hps_bs + (size_t)(2 * j + 1) * a.HW + ind] + row[3];
+        // channel ch of hps at this detection: from the map, or from the compact values of the winners
+        auto hp = [&](int ch) {
+            return a.chps ? a.chps[((size_t)b * a.K + k) * (2 * a.J) + ch] : a.hps[(size_t)b * a.hps_bs + (size_t)ch * a.HW + ind];
+        };
+        const float rx = hp(2 * j) + row[2];
+        const float ry = hp(2 * j + 1) + row[3];
         float best = __builtin_inff();
         int bi = 0;
         for (int c = 0; c < a.K; ++c) {
@@ -94,8 +103,8 @@ __global__ __launch_bounds__(128) void pose_match_kernel(PoseArgs a)
             bl = bt = __builtin_inff();
             br = bb = -__builtin_inff();
             for (int q = 0; q < a.J; ++q) {
-                const float qx = a.hps[(size_t)b * a.hps_bs + (size_t)(2 * q) * a.HW + ind] + row[2];
-                const float qy = a.hps[(size_t)b * a.hps_bs + (size_t)(2 * q + 1) * a.HW + ind] + row[3];
+                const float qx = hp(2 * q) + row[2];
+                const float qy = hp(2 * q + 1) + row[3];
                 bl = fminf(bl, qx); br = fmaxf(br, qx);
                 bt = fminf(bt, qy); bb = fmaxf(bb, qy);
             }
@@ -123,18 +132,21 @@ __global__ __launch_bounds__(128) void pose_score_kernel(PoseArgs a)
     a.out[(size_t)i * a.OW + 2 * a.J] = a.rows[(size_t)i * a.F] * (sum / (float)a.J);
 }
 
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
 // the joint heat-maps as B*J single-class images for ct_decode
-void joint_desc(const ct_pose_desc *d, ct_decode_desc *jd)
+void ct_pose_joint_desc(const ct_pose_desc *d, ct_decode_desc *jd)
 {
     *jd = ct_decode_desc();
     jd->hm = d->hm_hp; jd->B = d->B * d->num_joints; jd->C = 1; jd->h = d->h; jd->w = d->w; jd->K = d->K;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-int check(const ct_pose_desc *d, const char *who)
+// ``compact``: hps comes as values at the winners (ct_decode_pose_sparse), not as a map
+int ct_pose_check(const ct_pose_desc *d, const char *who, int compact)
 {
-    if (!d || !d->rows || !d->inds || !d->hps || !d->hm_hp) CT_FAIL_ARG("%s: null pointer", who);
+    if (!d || !d->rows || !d->inds || (!compact && !d->hps) || !d->hm_hp) CT_FAIL_ARG("%s: null pointer", who);
     if (d->B <= 0 || d->h <= 0 || d->w <= 0 || d->K <= 0 || d->num_joints <= 0) CT_FAIL_ARG("%s: bad shape", who);
     if (d->box_col != -1 && (d->box_col < 4 || d->box_col + 4 > d->row_floats))
         CT_FAIL_ARG("%s: box_col=%d is neither -1 (box from the heads / box-less) nor a box column of a %d-float row", who,
@@ -145,13 +157,11 @@ int check(const ct_pose_desc *d, const char *who)
     return CT_OK;
 }
 
-}  // namespace
-
 extern "C" size_t ct_decode_pose_workspace_bytes(const ct_pose_desc *d)
 {
-    if (check(d, "ct_decode_pose_workspace_bytes") != CT_OK) return 0;
+    if (ct_pose_check(d, "ct_decode_pose_workspace_bytes", 0) != CT_OK) return 0;
     ct_decode_desc jd;
-    joint_desc(d, &jd);
+    ct_pose_joint_desc(d, &jd);
     const size_t inner = ct_decode_workspace_bytes(&jd);
     if (!inner) return 0;
     const size_t BJK = (size_t)d->B * d->num_joints * d->K;
@@ -161,7 +171,7 @@ extern "C" size_t ct_decode_pose_workspace_bytes(const ct_pose_desc *d)
 
 extern "C" int ct_decode_pose(const ct_pose_desc *d, void *stream)
 {
-    int rc = check(d, "ct_decode_pose");
+    int rc = ct_pose_check(d, "ct_decode_pose", 0);
     if (rc != CT_OK) return rc;
     if (!d->out) CT_FAIL_ARG("ct_decode_pose: null output");
     const size_t need = ct_decode_pose_workspace_bytes(d);
@@ -176,14 +186,23 @@ extern "C" int ct_decode_pose(const ct_pose_desc *d, void *stream)
     int64_t *jinds = (int64_t *)ws;        ws += align256(BJK * sizeof(int64_t));
     float *sc = (float *)ws;               ws += align256(BJK * sizeof(float));
     ct_decode_desc jd;
-    joint_desc(d, &jd);
+    ct_pose_joint_desc(d, &jd);
     jd.out = jrows; jd.inds = jinds;
     jd.workspace = ws; jd.workspace_bytes = d->workspace_bytes - (size_t)(ws - (char *)d->workspace);
     rc = ct_decode(&jd, stream);           // 1. K peaks of every joint heat-map
     if (rc != CT_OK) return rc;
+    return ct_pose_match(d, jrows, jinds, sc, nullptr, nullptr, stream);
+}
+
+// steps 2 and 3 behind the joint decode.  ``chps`` / ``coff``: compact hps [B*K][2J] and offset [B*J*K][2] values read instead of
+// d->hps / d->hp_offset (ct_decode_pose_sparse; coff nullptr with chps: no offset head, +0.5)
+int ct_pose_match(const ct_pose_desc *d, const float *jrows, const int64_t *jinds, float *sc, const float *chps, const float *coff,
+                  void *stream)
+{
     PoseArgs a;
     const int HW = d->h * d->w;
-    a.rows = d->rows; a.inds = (const long long *)d->inds; a.hps = d->hps; a.off = d->hp_offset;
+    a.chps = chps; a.coff = coff;
+    a.rows = d->rows; a.inds = (const long long *)d->inds; a.hps = d->hps; a.off = chps ? nullptr : d->hp_offset;
     a.jrows = jrows; a.jinds = (const long long *)jinds; a.sc = sc; a.out = d->out;
     a.hps_bs = d->hps_batch_stride ? d->hps_batch_stride : (size_t)2 * d->num_joints * HW;
     a.off_bs = d->hp_offset_batch_stride ? d->hp_offset_batch_stride : (size_t)2 * HW;

@@ -107,6 +107,11 @@ def imread_bgr(path):
         return np.ascontiguousarray(np.asarray(im.convert('RGB'))[:, :, ::-1])
 
 
+def _own_option(opt, name, default=False):
+    """an option this package adds to the reference's namespace: optional whoever built ``opt``"""
+    return getattr(opt, name, default)
+
+
 def _prefetchable(prefetch, shape):
     """may ``prefetch`` be uploaded ahead into a frame slot: a contiguous float32 host tensor of the frames' ``shape``"""
     return (prefetch is not None and torch.is_tensor(prefetch) and prefetch.device.type == 'cpu'
@@ -173,7 +178,7 @@ class _FrameContext(object):
         with_hm = tracking and bool(getattr(det.opt, 'pre_hm', False))
         # detector, input size, image batch, launch plan and its prior inputs; is the prior heat map rendered from blobs
         self.det, self.hw, self.NB = det, (H, W), det.B * (2 if det.flip else 1)
-        self.plan = det.model.get_plan(self.NB, H, W, with_img, with_hm, True, det.sparse)
+        self.plan = det.model.get_plan(self.NB, H, W, with_img, with_hm, True, det.sparse, sparse_pose=det.sparse_pose)
         (_, self.img_in, self.hm_in), self.render = self.plan['inputs'], det.native and with_hm
         # flip_test: the arguments of ct_flip_merge; the maps the decode reads (the plan's outputs without flip_test)
         self.flip_call, self.merged = None, self.plan['outputs']
@@ -239,14 +244,17 @@ class _FrameContext(object):
         sparse = self.plan.get('sparse')
         if sparse is not None:
             sparse = dict(sparse, zero_tracking=bool(getattr(opt, 'zero_tracking', False)), flip=det.flip)
-        F = ops.Decoder.row_floats(dec_heads, [n for n, *_ in sparse['heads']] if sparse else None)
+        sparse_pose = self.plan.get('sparse_pose')
+        if sparse_pose is not None:
+            sparse_pose = dict(sparse_pose, flip=det.flip, flip_pairs=getattr(opt, 'flip_idx', COCO_FLIP_IDX))
+        F = ops.Decoder.row_floats(dec_heads, [n for n, *_ in sparse['heads']] if sparse else None, sparse_pose)
         self.host_out = torch.zeros((merged['hm'].shape[0], opt.K, F), dtype=torch.float32).pin_memory()
         # (round 3: the decode stores its rows straight into the pinned block and raises the end-of-frame flag itself --
         #  no D2H copy node and no flag kernel at the end of the frame graph; not with pose heads, whose kernels
         #  complete the rows after the decode)
         direct = HOST_FLAG and HOST_ROWS
         self.decoder = ops.Decoder(merged['hm'], dec_heads, opt.K, host_out=self.host_out if direct else None,
-                                   done_flag=self.done_flag if direct else None, sparse=sparse)
+                                   done_flag=self.done_flag if direct else None, sparse=sparse, sparse_pose=sparse_pose)
         assert tuple(self.decoder.out.shape) == tuple(self.host_out.shape)
         self.host_rows = self.host_out.numpy()
         if with_hm and not det.native:
@@ -445,6 +453,13 @@ class StreamDetector(object):
         # them, decode.py:99-180), 1/5 of the heads' work.  flip_test: hm is merged as a map, the averaged regression heads are
         # evaluated in both images at the winner and its mirrored pixel.  Not with pose heads (hm_hp is a heat-map).
         self.sparse = bool(getattr(opt, 'sparse_heads', False)) and not ({'hps', 'hm_hp'} & set(opt.heads))
+        # option sparse_pose_heads (opt-in, NOT a reference flag): the pose task's counterpart.  hm and hm_hp stay maps (both are
+        # decoded as heat-maps); hps is evaluated at the K winners and hp_offset (else reg) at the K peaks of every joint map
+        # (ct_decode_pose_sparse), reg / wh or ltrb / tracking at the winners like sparse_heads.  Not with an ltrb_amodal head:
+        # the match gates a snapped joint with the wh / ltrb box (decode.py:123,137), which the rows then do not hold, and no
+        # map is left to rebuild it from.  In every case it does not serve, the dense path runs unchanged.
+        self.sparse_pose = (bool(_own_option(opt, 'sparse_pose_heads')) and {'hm', 'hps', 'hm_hp'} <= set(opt.heads)
+                            and 'ltrb_amodal' not in opt.heads and int(getattr(self.model, 'head_conv', 0)) == 256)
         self.use_graph = use_graph
         self.trackers = [Tracker(opt) for _ in range(self.B)]
         # native host path (C++ post-process + association incl. the Hungarian / public-detection / pre_dets branches
@@ -1030,7 +1045,7 @@ def default_opt(heads, **kw):
         track_thresh=0.3, out_thresh=-1.0, pre_thresh=-1.0, new_thresh=0.3, max_age=-1, hungarian=False,
         public_det=False, zero_tracking=False, depth_scale=1.0, down_ratio=4, num_classes=heads['hm'],
         test_scales=[1.0], model_output_list=False, no_pause=True, dataset='', test_focal_length=-1,
-        input_h=512, input_w=512, fix_res=True, fix_short=0, pad=31)
+        input_h=512, input_w=512, fix_res=True, fix_short=0, pad=31, sparse_pose_heads=False)
     for k, v in kw.items():
         setattr(o, k, v)
     if o.tracking:

@@ -194,6 +194,10 @@ class DLASegHIP(torch.nn.Module):
             w0b = torch.cat([sd[h + '.0.weight'] for h in big], 0)
             P['hb_w'], P['hb_ww'] = ops.pack_weight(w0b), wino(w0b)
             P['hb_b'] = torch.cat([sd[h + '.0.bias'] for h in big], 0).contiguous()
+            if 'hm_hp' in big and big != ['hm_hp']:          # (sparse-pose plans: hm_hp is the only wide head left)
+                w0b = sd['hm_hp.0.weight']
+                P['hb_w:hm_hp'], P['hb_ww:hm_hp'] = ops.pack_weight(w0b), wino(w0b)
+                P['hb_b:hm_hp'] = sd['hm_hp.0.bias'].contiguous()
         # heads: all first layers share their input -> one 64 -> 256*nh conv
         w0 = torch.cat([sd[h + '.0.weight'] for h in self.heads], 0)
         P['head0_w'] = ops.pack_weight(w0)
@@ -216,14 +220,16 @@ class DLASegHIP(torch.nn.Module):
         # packed conv3x3 weights (the Winograd form has no single-pixel evaluation), hidden bias, [c, 256] output layer
         if hc == 256:
             for h, c in self.heads.items():
-                if h in _lib.HEAD_INDEX:
+                if h in _lib.HEAD_INDEX or h in ('hps', 'hp_offset'):
                     P['sparse.' + h] = (ops.pack_weight(sd[h + '.0.weight']), sd[h + '.0.bias'].contiguous(),
                                         sd[h + '.2.weight'].reshape(c, hc).contiguous(), sd[h + '.2.bias'].contiguous())
         self._prepared = P
         return P
 
-    def _build_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads=False, *, trunk_only=False):
-        """``trunk_only``: the plan stops at ``plan['feat']``, the 64-channel feature map, and has no head launches
+    def _build_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads=False, sparse_pose=False, *, trunk_only=False):
+        """``sparse_pose`` (opt-in, pose head sets): hm and hm_hp are the only dense head launches; reg / wh or ltrb / tracking
+        go to ``plan['sparse']`` like ``sparse_heads``, hps and the offset head to ``plan['sparse_pose']``.
+        ``trunk_only``: the plan stops at ``plan['feat']``, the 64-channel feature map, and has no head launches
         (heads.HeadFinetuner trains the heads on it)"""
         P = self._prepare()
         lib = _lib.load()
@@ -361,11 +367,28 @@ class DLASegHIP(torch.nn.Module):
         L.extend(dcn_launches)
 
         small, big = P['heads_small'], P['heads_big']
-        plan['sparse'] = None
+        plan['sparse'] = plan['sparse_pose'] = None
+        if sparse_pose:
+            # hps is read at the K winners and the offset head at the K peaks of each joint map (decode.py:161-167, 21-28):
+            # ct_decode_pose_sparse evaluates them there.  hm keeps the launch form of the sparse plans ('hs:hm'), hm_hp its
+            # dense form (conv3x3 + 1x1 tail with the sigmoid), so winners and peaks are the dense path's
+            hs = set(self.heads)
+            if (sparse_heads or not {'hm', 'hps', 'hm_hp'} <= hs or 'ltrb_amodal' in hs or 'sparse.hps' not in P or not fuse_sigmoid
+                    or 'hm' not in small or 'hm_hp' not in big):
+                raise _lib.CTError('sparse pose heads need hm, hps and hm_hp heads with head_conv 256, no ltrb_amodal head '
+                                   '(the match finds its gate box in the packed row) and the detector\'s fused epilogues')
+            sp = [h for h in self.heads if h in _lib.HEAD_INDEX and ('sparse.' + h) in P]
+            if 'ltrb' in hs:                                    # (dead heads, as below)
+                sp = [h for h in sp if h not in ('reg', 'wh')]
+            if sp:
+                plan['sparse'] = {'feat': feat, 'heads': [(h,) + P['sparse.' + h] for h in sp], 'depth_scale': self.depth_scale}
+            off = 'hp_offset' if 'hp_offset' in hs else 'reg' if 'reg' in hs else None
+            plan['sparse_pose'] = {'feat': feat, 'hps': P['sparse.hps'], 'off': P['sparse.' + off] if off else None}
+            small, big = ['hm'], ['hm_hp']
         if sparse_heads:
             # opt-in (detector only, never Module.forward): the regression heads the decode reads at the K winners are not
             # computed as maps -- ct_decode evaluates them at those pixels (ct_sparse_heads_desc)
-            sp = [h for h in self.heads if ('sparse.' + h) in P]
+            sp = [h for h in self.heads if h in _lib.HEAD_INDEX and ('sparse.' + h) in P]
             if {'ltrb', 'ltrb_amodal'} & set(self.heads):
                 # dead heads: generic_decode overwrites the wh box with the ltrb / ltrb_amodal box (decode.py:131-139,150-159)
                 # and `reg` only feeds the wh box (decode.py:102-110) -- neither reaches the returned dict, so with the
@@ -375,11 +398,11 @@ class DLASegHIP(torch.nn.Module):
                 raise _lib.CTError('sparse heads need an hm head, regression heads with head_conv 256, no pose heads '
                                    'and the detector\'s fused epilogues')
             plan['sparse'] = {'feat': feat, 'heads': [(h,) + P['sparse.' + h] for h in sp], 'depth_scale': self.depth_scale}
-            small = [h for h in small if ('sparse.' + h) not in P]          # (the dead heads leave the dense launch too)
-            if any(('sparse.' + h) in P for h in big):          # (more small heads than one fused launch holds: not with sparse heads)
+            small = [h for h in small if not (h in _lib.HEAD_INDEX and ('sparse.' + h) in P)]          # (the dead heads leave the dense launch too)
+            if any(h in _lib.HEAD_INDEX and ('sparse.' + h) in P for h in big):          # (more small heads than one fused launch holds: not with sparse heads)
                 raise _lib.CTError('sparse heads: %s do not fit the fused-heads launch' % [h for h in big if ('sparse.' + h) in P])
         if trunk_only:
-            if sparse_heads:
+            if sparse_heads or sparse_pose:
                 raise _lib.CTError('a trunk-only plan has no heads, sparse or dense')
             outputs = OrderedDict()
         elif small or plan['sparse'] is not None:
@@ -467,7 +490,9 @@ class DLASegHIP(torch.nn.Module):
                              us=100.0))
         if big:
             mid = ops.new_view(N, feat.H, feat.W, hc * len(big), dev)
-            d = ops.make_conv_desc(feat, P['hb_w'], hc * len(big), 3, 1, shift=P['hb_b'], relu=True, out=mid, w_wino=P['hb_ww'])
+            sfx = '' if big == P['heads_big'] else ':' + ','.join(big)      # (a sparse-pose plan keeps hm_hp alone)
+            d = ops.make_conv_desc(feat, P['hb_w' + sfx], hc * len(big), 3, 1, shift=P['hb_b' + sfx], relu=True, out=mid,
+                                   w_wino=P['hb_ww' + sfx])
             us = autotune.tune_conv(d, dev)[2] if tune else 100.0
             L.append(_Launch('heads.0', 'conv', d, (feat, mid), us=us, ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
             for j, h in enumerate(big):
@@ -696,10 +721,10 @@ class DLASegHIP(torch.nn.Module):
                 parts.append('%s:%s' % (l.name, l.fn))
         return ';'.join(parts)
 
-    def get_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid=False, sparse_heads=False, *, trunk_only=False):
-        key = (N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads, trunk_only)
+    def get_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid=False, sparse_heads=False, *, trunk_only=False, sparse_pose=False):
+        key = (N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads, trunk_only) + (('sparse_pose',) if sparse_pose else ())
         if key not in self._plans:
-            self._plans[key] = self._build_plan(*key[:7], trunk_only=trunk_only)
+            self._plans[key] = self._build_plan(*key[:7], sparse_pose, trunk_only=trunk_only)
         return self._plans[key]
 
     def forward_plan(self, plan, x, pre_img=None, pre_hm=None):

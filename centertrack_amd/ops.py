@@ -5,6 +5,7 @@
 (reference ``Root.forward``, dla.py:164-166) never copy."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib, _train          # (_train imports this module in turn: each reads the other at call time only)
@@ -886,19 +887,28 @@ class Decoder(object):
     pose task, by the refined key points [2J] and ``kps_score`` [1]."""
 
     @staticmethod
-    def row_floats(heads, sparse=None):
-        """floats per packed row for this set of heads (the pose fields included; ``sparse``: names of sparse heads)"""
+    def row_floats(heads, sparse=None, sparse_pose=None):
+        """floats per packed row for this set of heads (the pose fields included; ``sparse``: names of sparse heads;
+        ``sparse_pose``: the argument of that name of the constructor -- the same rows as with an ``hps`` map)"""
         _, F = decode_layout([n for n in heads if n in _lib.HEAD_INDEX] + list(sparse or ()))
         if 'hps' in heads and 'hm_hp' in heads:
             F += heads['hps'].shape[1] + 1
+        elif sparse_pose is not None and 'hm_hp' in heads:
+            F += 2 * heads['hm_hp'].shape[1] + 1
         return F
 
-    def __init__(self, hm, heads, K, host_out=None, done_flag=None, sparse=None):
+    def __init__(self, hm, heads, K, host_out=None, done_flag=None, sparse=None, sparse_pose=None):
         """``host_out`` (pinned host float32 [B,K,F]) / ``done_flag`` (pinned host int32): the decode also stores the
         rows straight into host memory and raises the flag when they are complete (no pose heads).
         ``sparse`` (round 5, opt-in): ``{'feat': NHWC view of the 64-channel feature map, 'heads': [(name, w1_packed, b1,
         w2 [c,256], b2)], 'depth_scale', 'zero_tracking'}`` -- these regression heads have no map in ``heads``; they are
-        evaluated at the K winners only (ct_sparse_heads_desc)"""
+        evaluated at the K winners only (ct_sparse_heads_desc).
+        ``sparse_pose`` (opt-in, independent of ``sparse``): ``{'feat': that NHWC view, 'hps': (w1_packed, b1, w2 [2J,256],
+        b2), 'off': the same of the hp_offset head (else the reg head) with w2 [2,256], or None for +0.5, 'flip': bool,
+        'flip_pairs': int pairs}`` -- ``heads`` holds ``hm_hp`` but neither ``hps`` nor ``hp_offset``; ``hps`` is evaluated
+        at the K winners and the offset head at the K peaks of every joint map (ct_decode_pose_sparse).  Same row layout
+        as with the two maps.  A ``reg`` map in ``heads`` only serves the gate box then.  With ``sparse`` the match needs
+        its gate box in the rows: no ``ltrb_amodal`` head."""
         lib = _lib.load()
         self.K = K
         B, C, h, w = hm.shape
@@ -937,7 +947,15 @@ class Decoder(object):
                                             ([n for n, *_ in sparse['heads']] if sparse is not None else []))
         F0 = self.F
         assert lib.ct_decode_row_floats(ctypes.byref(d)) == F0
-        self.pose = None
+        self.pose = self.pose_sparse = None
+        if sparse_pose is not None:
+            if 'hps' in heads or 'hp_offset' in heads or 'hm_hp' not in heads:
+                raise _lib.CTError('sparse pose heads: `heads` holds hm_hp and neither hps nor hp_offset')
+            if sparse is not None and 'ltrb_amodal' in [n for n, *_ in sparse['heads']]:
+                raise _lib.CTError('sparse pose heads beside a sparse ltrb_amodal head: the rows do not hold the gate box')
+            J = heads['hm_hp'].shape[1]
+            self.layout = self.layout + [('hps', F0, 2 * J), ('kps_score', F0 + 2 * J, 1)]
+            self.F = F0 + 2 * J + 1
         if 'hps' in heads:                                 # pose branch, decode.py:161-171
             J = heads['hps'].shape[1] // 2
             if 'hm_hp' in heads:
@@ -956,22 +974,31 @@ class Decoder(object):
         d.out_stride = self.F
         d.workspace, d.workspace_bytes = self.ws.data_ptr(), nbytes
         self.direct = False
-        if host_out is not None and done_flag is not None and 'hps' not in heads:
+        if host_out is not None and done_flag is not None and 'hps' not in heads and sparse_pose is None:
             assert tuple(host_out.shape) == (B, K, self.F) and host_out.is_pinned() and done_flag.is_pinned()
             self.done_counter = torch.zeros((4,), dtype=torch.int32, device=hm.device)
             d.host_out, d.done_flag = host_out.data_ptr(), done_flag.data_ptr()
             d.done_counter = self.done_counter.data_ptr()
             self.direct = True
         self.desc = d
-        if 'hps' in heads:
-            hps, hm_hp = heads['hps'], heads['hm_hp']
-            off = heads.get('hp_offset', heads.get('reg'))
-            assert planes_ok(hps) and hm_hp.is_contiguous() and hm_hp.shape[1] == J and (off is None or planes_ok(off))
-            pd = _lib.PoseDesc()
+        if 'hps' in heads or sparse_pose is not None:
+            hm_hp = heads['hm_hp']
+            assert hm_hp.is_contiguous() and hm_hp.shape[1] == J
+            if sparse_pose is not None:
+                hps = off = None
+                spd = _lib.PoseSparseDesc()
+                pd = spd.base
+            else:
+                hps = heads['hps']
+                off = heads.get('hp_offset', heads.get('reg'))
+                assert planes_ok(hps) and (off is None or planes_ok(off))
+                pd = _lib.PoseDesc()
             pd.rows, pd.row_floats, pd.inds = self.out.data_ptr(), self.F, self.inds.data_ptr()
             # the gate box of _update_kps_with_hm is generic_decode's local `bboxes`: wh, overridden by ltrb -- never the
             # ltrb_amodal box that replaces ret['bboxes'] in the packed row (decode.py:123,137 vs 159)
-            if 'ltrb_amodal' in heads or not ({'wh', 'ltrb'} & set(heads)):
+            # (sparse main heads: the rows are the only place the box is -- column 4, or the box-less variant)
+            in_rows = set(heads) | set(n for n, *_ in sparse['heads']) if sparse is not None else set(heads)
+            if 'ltrb_amodal' in in_rows or not ({'wh', 'ltrb'} & in_rows):
                 pd.box_col = -1
                 for name, fld in (('wh', 'box_wh'), ('ltrb', 'box_ltrb')):
                     if name in heads:
@@ -983,10 +1010,30 @@ class Decoder(object):
             else:
                 pd.box_col = 4
             pd.B, pd.h, pd.w, pd.K, pd.num_joints = B, h, w, K, J
-            pd.hps, pd.hm_hp, pd.hp_offset = hps.data_ptr(), hm_hp.data_ptr(), _p(off)
-            pd.hps_batch_stride = hps.stride(0)
+            pd.hps, pd.hm_hp, pd.hp_offset = _p(hps), hm_hp.data_ptr(), _p(off)
+            pd.hps_batch_stride = hps.stride(0) if hps is not None else 0
             pd.hp_offset_batch_stride = off.stride(0) if off is not None else 0
             pd.out, pd.out_stride = self.out.data_ptr() + 4 * F0, self.F
+            if sparse_pose is not None:
+                feat, flip = sparse_pose['feat'], bool(sparse_pose.get('flip'))
+                assert feat.C == 64 and (feat.N, feat.H, feat.W) == ((2 * B if flip else B), h, w)
+                spd.feat, spd.ldf, spd.flip_B = feat.ptr, feat.ld, B if flip else 0
+                for pre, c, wts in (('hps', 2 * J, sparse_pose['hps']), ('off', 2, sparse_pose.get('off'))):
+                    if wts is not None:
+                        w1, b1, w2, b2 = wts
+                        assert tuple(w2.shape) == (c, 256) and w2.is_contiguous() and b1.numel() == 256 and b2.numel() == c
+                        for fld, t in zip(('w1', 'b1', 'w2', 'b2'), wts):
+                            setattr(spd, '%s_%s' % (pre, fld), t.data_ptr())
+                pairs = np.ascontiguousarray(sparse_pose.get('flip_pairs', ()), np.int32).reshape(-1, 2)
+                spd.flip_pairs, spd.num_pairs = pairs.ctypes.data, len(pairs)
+                need = ctypes.c_size_t(0)
+                _lib.check(lib.ct_decode_pose_sparse_workspace_bytes(ctypes.byref(spd), ctypes.byref(need)),
+                           'ct_decode_pose_sparse_workspace_bytes')
+                # (zeroed: the values of an absent offset head are then defined too)
+                self.pose_ws = torch.zeros(need.value // 8 + 1, dtype=torch.int64, device=hm.device)
+                pd.workspace, pd.workspace_bytes = self.pose_ws.data_ptr(), self.pose_ws.numel() * 8
+                self.pose_sparse = (spd, sparse_pose, pairs)            # (keeps the tensors and the pairs alive)
+                return
             pbytes = lib.ct_decode_pose_workspace_bytes(ctypes.byref(pd))
             if pbytes == 0:
                 _lib.check(1, 'ct_decode_pose_workspace_bytes')
@@ -998,7 +1045,21 @@ class Decoder(object):
         _lib.check(_lib.load().ct_decode(ctypes.byref(self.desc), _lib.stream_ptr()), 'ct_decode')
         if self.pose is not None:
             _lib.check(_lib.load().ct_decode_pose(ctypes.byref(self.pose), _lib.stream_ptr()), 'ct_decode_pose')
+        if self.pose_sparse is not None:
+            _lib.check(_lib.load().ct_decode_pose_sparse(ctypes.byref(self.pose_sparse[0]), _lib.stream_ptr()),
+                       'ct_decode_pose_sparse')
         return self.out
+
+    def pose_values(self):
+        """what the match of the last ``run`` read instead of maps (``sparse_pose``): the merged raw ``hps`` values [B,K,2J] at
+        the winners, before the centre is added, and the offset values [B*J,K,2] at the joint peaks (None without an offset
+        head) -- views of the workspace"""
+        spd = self.pose_sparse[0]
+        B, K, J = spd.base.B, spd.base.K, spd.base.num_joints
+        f = self.pose_ws.view(torch.float32)
+        n = B * K * 2 * J
+        at = ((n * 4 + 255) // 256) * 64
+        return f[:n].view(B, K, 2 * J), (f[at:at + B * J * K * 2].view(B * J, K, 2) if spd.off_w1 else None)
 
     def unpack(self, packed):
         """packed [B,K,F] (torch or numpy) -> the reference's ``dets`` dict (decode.py:99-180)."""

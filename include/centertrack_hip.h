@@ -656,6 +656,29 @@ typedef struct ct_pose_desc {
 } ct_pose_desc;
 size_t ct_decode_pose_workspace_bytes(const ct_pose_desc *d);
 int ct_decode_pose(const ct_pose_desc *d, void *stream);
+/* Sparse pose heads (opt-in; no reference equivalent): ct_decode_pose without the hps and offset maps.  The reference reads
+ * hps at the K winners (decode.py:161-167) and the offset head at the K peaks of every joint map (decode.py:21-28); here
+ * both heads are evaluated at exactly those pixels from their weights -- conv3x3 64 -> 256 (zero padding) + bias + ReLU +
+ * conv1x1 + bias over feat, the NHWC feature map of ct_sparse_heads_desc (same feat / ldf / flip_B semantics).
+ * base: as for ct_decode_pose, with hps and hp_offset NULL; hm_hp stays a dense map (the merged one when flip_B > 0) and
+ * the gate box comes from the rows (box_col) or the box maps as before.
+ * hps_*: w1 in ct_pack_conv_weight layout [256,64,3,3], b1 [256], w2 [2J][256] row-major, b2 [2J].  off_*: the hp_offset
+ * head (else the reg head) likewise with w2 [2][256]; all four NULL = no offset head (+0.5).
+ * flip_B > 0: hps is also evaluated in image flip_B + b at the mirrored pixel (y, w-1-x) and merged like ct_flip_merge's
+ * CT_FLIP_JOINT_OFFSETS with the HOST joint pairs flip_pairs [num_pairs][2]; the offset head reads image b alone.
+ * 1 <= num_joints <= 32.  Launches: the joint decode, the point evaluation, its reduction, match, score -- all on `stream`,
+ * no host wait, bitwise reproducible.  Every argument error returns before the first launch.
+ * The workspace begins with the values the match read: merged hps [B,K,2J] floats (before the centre is added), then at
+ * the next multiple of 256 bytes the offsets [B*J,K,2] (undefined without an offset head). */
+typedef struct ct_pose_sparse_desc {
+    ct_pose_desc base;
+    const float *feat; int ldf; int flip_B;
+    const float *hps_w1, *hps_b1, *hps_w2, *hps_b2;
+    const float *off_w1, *off_b1, *off_w2, *off_b2;
+    const int *flip_pairs; int num_pairs;
+} ct_pose_sparse_desc;
+int ct_decode_pose_sparse_workspace_bytes(const ct_pose_sparse_desc *d, size_t *bytes);
+int ct_decode_pose_sparse(const ct_pose_sparse_desc *d, void *stream);
 
 /* ---- prior heat-map rendering on device ------------------------------------------------
  * Replaces the numpy Gaussian splatting + full-map H2D of Detector._get_additional_inputs
