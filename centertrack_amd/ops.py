@@ -968,7 +968,8 @@ class Decoder(object):
         nbytes = lib.ct_decode_workspace_bytes(ctypes.byref(d))
         if nbytes == 0:
             _lib.check(1, 'ct_decode_workspace_bytes')
-        # (zeroed: the block holds a reserved counter area besides the keys -- nothing in it is ever read uninitialised)
+        # (zeroed for tidiness only: ct_decode writes every byte it reads -- candidates, winner keys, partials -- and the one
+        #  extra word past ``nbytes`` is never handed to it)
         self.ws = torch.zeros(nbytes // 8 + 1, dtype=torch.int64, device=hm.device)
         d.out, d.inds = self.out.data_ptr(), self.inds.data_ptr()
         d.out_stride = self.F
@@ -1029,7 +1030,8 @@ class Decoder(object):
                 need = ctypes.c_size_t(0)
                 _lib.check(lib.ct_decode_pose_sparse_workspace_bytes(ctypes.byref(spd), ctypes.byref(need)),
                            'ct_decode_pose_sparse_workspace_bytes')
-                # (zeroed: the values of an absent offset head are then defined too)
+                # (zeroed only so that the offsets area reads as 0 without an offset head: the call neither writes nor reads it
+                #  then, and of everything else it reads nothing it has not written)
                 self.pose_ws = torch.zeros(need.value // 8 + 1, dtype=torch.int64, device=hm.device)
                 pd.workspace, pd.workspace_bytes = self.pose_ws.data_ptr(), self.pose_ws.numel() * 8
                 self.pose_sparse = (spd, sparse_pose, pairs)            # (keeps the tensors and the pairs alive)

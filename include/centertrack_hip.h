@@ -587,7 +587,10 @@ enum { CT_HEAD_REG = 0, CT_HEAD_WH, CT_HEAD_TRACKING, CT_HEAD_LTRB, CT_HEAD_LTRB
  * head[i] = CT_HEAD_* id; w1 = conv3x3 64 -> 256 weights in ct_pack_conv_weight layout, b1 [256]; w2 = conv1x1 weights
  * [c][256] row-major, b2 [c].  The dep head gets the dense epilogue's transform (1 / (sigmoid(v) + 1e-6) - 1) *
  * depth_scale (detector.py:305-307); zero_tracking != 0 zeroes the tracking output (decode.py:95-96).  Two launches behind
- * the selection: the heads' partial products at the winners, then the rows (+ host copy + end-of-frame flag). */
+ * the selection: the heads' partial products at the winners, then the rows (+ host copy + end-of-frame flag).
+ * The workspace of ct_decode is scratch from end to end, with or without sparse heads: candidate slots, winner keys [B][K]
+ * and the partials are each written by the call before it reads them, so the caller need not clear any byte of it.  The
+ * one thing that must be zero before the first launch is *done_counter, which is not part of the workspace. */
 typedef struct ct_sparse_heads_desc {
     const float *feat; int ldf;
     int nheads;
@@ -669,7 +672,8 @@ int ct_decode_pose(const ct_pose_desc *d, void *stream);
  * 1 <= num_joints <= 32.  Launches: the joint decode, the point evaluation, its reduction, match, score -- all on `stream`,
  * no host wait, bitwise reproducible.  Every argument error returns before the first launch.
  * The workspace begins with the values the match read: merged hps [B,K,2J] floats (before the centre is added), then at
- * the next multiple of 256 bytes the offsets [B*J,K,2] (undefined without an offset head). */
+ * the next multiple of 256 bytes the offsets [B*J,K,2] (undefined without an offset head: never written, never read).
+ * Like ct_decode's, the workspace is scratch from end to end: no byte of it has to be cleared by the caller. */
 typedef struct ct_pose_sparse_desc {
     ct_pose_desc base;
     const float *feat; int ldf; int flip_B;

@@ -146,14 +146,14 @@ COCO_FLIP_IDX = [[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [1
 def mirror_joints(x, flip_idx, offsets):
     """model/utils.py:33-50 (flip_lr / flip_lr_off): mirror a joint map left-right -- reverse the width axis,
     exchange the left/right joints and, for offset maps (``offsets``: channels are (dx, dy) per joint),
-    negate dx."""
+    negate dx.  The exchanges are successive, each on the result of the one before, as the reference's in-place loop
+    over flip_idx makes them: a list whose pairs share a joint is not the same as swapping from a snapshot."""
     out = torch.flip(x, [3]).clone()
     if offsets:
         out = out.view(out.shape[0], -1, 2, out.shape[2], out.shape[3])
         out[:, :, 0] *= -1
-    src = out.clone()
     for a, b in flip_idx:
-        out[:, a], out[:, b] = src[:, b], src[:, a]
+        out[:, a], out[:, b] = out[:, b].clone(), out[:, a].clone()
     return out.reshape(x.shape)
 
 

@@ -15,10 +15,11 @@ import _sparse_pose as SP
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 
 
-@pytest.mark.parametrize('J,pairs', [(17, SP.COCO_PAIRS), (4, [(0, 1), (2, 3)])])
+@pytest.mark.parametrize('J,pairs', [(17, SP.COCO_PAIRS), (4, [(0, 1), (2, 3)]), (4, SP.OVERLAPPING_PAIRS), (1, [])])
 def test_point_merge_equals_the_oracles_merged_map_at_the_points(J, pairs):
     """the reference the GPU tests trust: merging hps point by point == gathering the map the oracle merges
-    (flip_output -> mirror_joints(offsets=True)), exactly, in float64"""
+    (flip_output -> mirror_joints(offsets=True)), exactly, in float64 -- also for pairs that share a joint, where both follow
+    the reference's successive in-place swaps (utils.py:47-49) and a swap from a snapshot gives another map"""
     from oracle import detector as odet
     g = torch.Generator().manual_seed(J)
     B, h, w, K = 2, 7, 10, 30
@@ -31,6 +32,18 @@ def test_point_merge_equals_the_oracles_merged_map_at_the_points(J, pairs):
         merged = odet.flip_output({'hps': torch.stack((m[b], m[B + b]))}, [list(p) for p in pairs])['hps']
         want = SP.gather_points(merged, torch.zeros(K, dtype=torch.long), inds[b])
         assert torch.equal(got[b * K:(b + 1) * K], want)
+
+
+def test_pairs_that_share_a_joint_are_swapped_one_after_the_other():
+    """[(0, 1), (1, 2), (0, 3)] worked by hand: [0,1,2,3] -> [1,0,2,3] -> [1,2,0,3] -> [3,2,0,1], so the merged joint j reads the
+    mirrored joint (3, 2, 0, 1)[j]; swapping from a snapshot would give (3, 2, 1, 0)"""
+    from oracle import detector as odet
+    b = torch.arange(1.0, 9.0, dtype=torch.float64).view(1, 8)
+    got = SP.merge_points(torch.zeros((1, 8), dtype=torch.float64), b, SP.OVERLAPPING_PAIRS) * 2
+    want = torch.tensor([[-7.0, 8.0, -5.0, 6.0, -1.0, 2.0, -3.0, 4.0]], dtype=torch.float64)
+    assert torch.equal(got, want)
+    m = odet.mirror_joints(b.view(1, 8, 1, 1), [list(p) for p in SP.OVERLAPPING_PAIRS], True)
+    assert torch.equal(m.view(1, 8), want)
 
 
 def test_row_layout_equals_the_dense_pose_layout():
