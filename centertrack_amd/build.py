@@ -25,7 +25,7 @@ def build(force=False, verbose=False):
     objdir = os.path.join(PKG, 'build')
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, 'ct_common.h'), os.path.join(CSRC, 'ksplit_core.h'), os.path.join(CSRC, 'ct_train.h'),
-               os.path.join(CSRC, 'ct_warp.h'), os.path.join(ROOT, 'include', 'centertrack_hip.h')]
+               os.path.join(CSRC, 'ct_warp.h'), os.path.join(CSRC, 'point_heads.h'), os.path.join(ROOT, 'include', 'centertrack_hip.h')]
     objs = []
     procs = []
     for src in SOURCES:

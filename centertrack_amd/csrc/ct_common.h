@@ -61,6 +61,28 @@ int ct_pose_check(const ct_pose_desc *d, const char *who, int compact);
 void ct_pose_joint_desc(const ct_pose_desc *d, ct_decode_desc *jd);
 int ct_pose_match(const ct_pose_desc *d, const float *jrows, const int64_t *jinds, float *sc, const float *chps, const float *coff,
                   void *stream);
+// What ct_sparse_heads_desc (decode.hip) and ct_pose_sparse_desc (sparse_pose.hip) share: the feature view -- 16-byte aligned
+// NHWC, >= 64 channels at a pitch of whole float4s, B images or 2 * B with the mirrored twins behind (flip_B) ...
+static inline int ct_check_sparse_feat(const char *who, const float *feat, int ldf, int flip_B, int B)
+{
+    if (!feat || ((uintptr_t)feat & 15) || ldf < 64 || (ldf & 3))
+        CT_FAIL_ARG("%s: sparse heads need a 16-byte aligned NHWC feature view of >= 64 channels (pitch a multiple of 4)", who);
+    if (flip_B < 0 || (flip_B > 0 && flip_B != B)) CT_FAIL_ARG("%s: sparse flip_B must be 0 or B (feat then holds 2 * B images)", who);
+    return CT_OK;
+}
+// ... and a head's four weight pointers: all of them, or with `optional` none
+static inline bool ct_sparse_head_ok(const float *w1, const float *b1, const float *w2, const float *b2, bool optional)
+{
+    const int n = !!w1 + !!b1 + !!w2 + !!b2;
+    return n == 4 || (optional && n == 0);
+}
+
+// channels of regression head hd (CT_HEAD_*): the one table behind the packed row, the dense gather and the sparse heads
+__host__ __device__ constexpr int ct_head_ch(int hd)
+{
+    constexpr int ch[CT_NUM_HEADS] = {2, 2, 2, 4, 4, 1, 8, 3, 2, 8, 3};
+    return ch[hd];
+}
 
 // XCD-aware decode of the linear workgroup id into (cout block, pixel-tile index).  Workgroups are dealt to
 // the 8 XCDs round-robin (id % 8) and each XCD has its own 4 MB L2, so with `per` = coutBlocks / 8 > 0

@@ -24,6 +24,7 @@
 //            over ALL pixels with the NMS recomputed from HBM (slow, exact, rare).
 // Byte/index work: HBM/L2-bound, no matrix cores.
 #include "ct_common.h"
+#include "point_heads.h"
 
 namespace {
 CT_DEFINE_STAMPS(decode)    // (tools/decode_phases.py; expands to nothing in the shipped build)
@@ -39,6 +40,14 @@ __device__ __forceinline__ unsigned f2ord(float f)
 __device__ __forceinline__ float ord2f(unsigned o)
 {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+struct Winner { float score; int cls, p, y, x; };     // a final-form key (score bits : ~(class * HW + pixel)) taken apart
+__device__ __forceinline__ Winner key_winner(unsigned long long k, int HW, int w)
+{
+    const unsigned flat = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
+    const int cls = (int)(flat / (unsigned)HW), p = (int)(flat - (unsigned)cls * (unsigned)HW), y = p / w;
+    return Winner{ord2f((unsigned)(k >> 32)), cls, p, y, p - y * w};
 }
 
 // histogram increment with same-digit lanes of a wave combined into one LDS atomic (scores of a
@@ -199,7 +208,6 @@ struct Stage2Args {
     const unsigned long long *cand;
     const float *hm;
     const float *heads[CT_NUM_HEADS];
-    int head_ch[CT_NUM_HEADS];
     size_t head_bs[CT_NUM_HEADS];   // floats between consecutive images of each head map
     size_t hm_bs;
     float *out;
@@ -223,7 +231,6 @@ template <typename HV>
 __device__ __forceinline__ void emit_row(float *row, float *hrow, unsigned present, float score, int cls, float xs0,
                                          float ys0, HV hv)
 {
-    constexpr int HCH[CT_NUM_HEADS] = {2, 2, 2, 4, 4, 1, 8, 3, 2, 8, 3};
     auto has = [&](int hd) { return (present >> hd) & 1u; };
     int f = 0;
     // (round 4: assembling the rows in LDS and storing them coalesced was measured and dropped -- the host copy's cost
@@ -262,7 +269,7 @@ __device__ __forceinline__ void emit_row(float *row, float *hrow, unsigned prese
         const int hd = rest[q];
         if (!has(hd)) continue;
 #pragma unroll
-        for (int ch = 0; ch < HCH[hd]; ++ch) put(hv(hd, ch));
+        for (int ch = 0; ch < ct_head_ch(hd); ++ch) put(hv(hd, ch));
     }
 }
 
@@ -720,7 +727,7 @@ __global__ __launch_bounds__(1024) void decode_stage2_kernel(Stage2Args a)
         for (int r = threadIdx.x; r < a.K; r += blockDim.x) {
             const unsigned long long k = win[r];
             a.winners[(size_t)b * a.K + r] = k;
-            if (a.inds) a.inds[(size_t)b * a.K + r] = (int)((0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)) % (unsigned)HW);
+            if (a.inds) a.inds[(size_t)b * a.K + r] = key_winner(k, HW, a.w).p;
         }
         CT_STAMP(5);
         CT_STAMP(6);
@@ -729,28 +736,22 @@ __global__ __launch_bounds__(1024) void decode_stage2_kernel(Stage2Args a)
         return;
     }
     for (int r = threadIdx.x; r < a.K; r += blockDim.x) {
-        const unsigned long long k = win[r];
-        const float score = ord2f((unsigned)(k >> 32));
-        const unsigned flat = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
-        const int cls = (int)(flat / (unsigned)HW);
-        const int p = (int)(flat - (unsigned)cls * (unsigned)HW);
-        const float ys0 = (float)(p / a.w), xs0 = (float)(p % a.w);
+        const Winner wn = key_winner(win[r], HW, a.w);
         float *row = a.out + ((size_t)b * a.K + r) * a.F;
         float *hrow = a.host_out ? a.host_out + ((size_t)b * a.K + r) * a.F : nullptr;
-        if (a.inds) a.inds[(size_t)b * a.K + r] = p;
+        if (a.inds) a.inds[(size_t)b * a.K + r] = wn.p;
         // every head value of this row is fetched up front, branch-free (absent heads read hm[0] and are
         // ignored): ~39 independent loads in flight instead of a chain of dependent round trips
-        constexpr int HCH[CT_NUM_HEADS] = {2, 2, 2, 4, 4, 1, 8, 3, 2, 8, 3};
         float hval[CT_NUM_HEADS][8];
 #pragma unroll
         for (int hd = 0; hd < CT_NUM_HEADS; ++hd) {
             const float *hp = a.heads[hd];
             const bool on = hp != nullptr;
-            const float *base = on ? hp + (size_t)b * a.head_bs[hd] + p : a.hm;
+            const float *base = on ? hp + (size_t)b * a.head_bs[hd] + wn.p : a.hm;
 #pragma unroll
-            for (int ch = 0; ch < HCH[hd]; ++ch) hval[hd][ch] = base[on ? (size_t)ch * HW : 0];
+            for (int ch = 0; ch < ct_head_ch(hd); ++ch) hval[hd][ch] = base[on ? (size_t)ch * HW : 0];
         }
-        emit_row(row, hrow, a.present, score, cls, xs0, ys0, [&](int hd, int ch) { return hval[hd][ch]; });
+        emit_row(row, hrow, a.present, wn.score, wn.cls, (float)wn.x, (float)wn.y, [&](int hd, int ch) { return hval[hd][ch]; });
     }
     CT_STAMP(5);
     if (a.done_flag) {
@@ -765,14 +766,11 @@ __global__ __launch_bounds__(1024) void decode_stage2_kernel(Stage2Args a)
 // generic_decode reads the regression heads (reg, wh, tracking, ltrb*, dep, rot, dim, amodel_offset, ...) at the K winner
 // pixels ONLY (decode.py:99-180: every one of them goes through _tranpose_and_gather_feat(head, inds)); the reference
 // still computes their dense maps because a framework conv has no other form.  With ct_decode_desc.sparse the maps are
-// never made: after the selection this kernel evaluates conv3x3 64 -> 256 + bias + ReLU + conv1x1 256 -> c of every
-// listed head at the winners -- a [16 winners x 576] x [576 x 256] MFMA product per (workgroup, head), the winner's
-// 3x3 x 64 patch gathered from the NHWC feature map (zero outside the map: padding 1) -- applies the dense epilogue's
-// transforms (dep: detector.py:305-307) and assembles the packed rows exactly like the dense gather (emit_row).
-// One workgroup = 16 waves = 16 winners of one image x ALL sparse heads; wave w owns hidden channels 16w .. 16w+15.
+// never made: after the selection sparse_heads_kernel evaluates conv3x3 64 -> 256 + bias + ReLU + conv1x1 256 -> c of every
+// listed head at the winners -- the point core of point_heads.h, the winner's 3x3 x 64 patch gathered from the NHWC feature
+// map (zero outside the map: padding 1) -- and sparse_rows_kernel applies the dense epilogue's transforms (dep:
+// detector.py:305-307) and assembles the packed rows exactly like the dense gather (emit_row).
 // 4 heads x 100 winners = 0.12 GFLOP instead of 9.7 GFLOP of dense maps at 512 x 512.
-constexpr int SP_HID = 256;          // hidden channels of a head (head_conv, opts.py:294-295)
-
 struct SparseArgs {
     const float *feat; int ldf; size_t feat_bs;
     int nheads;
@@ -798,10 +796,9 @@ struct SparseArgs {
 // next launch) sums them in quarter order (deterministic), applies bias / transforms and assembles the rows.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void sparse_heads_kernel(SparseArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float A[36 * 256];            // [tap * 4 + slab][16 winners][16 ch], swizzled
-    __shared__ __attribute__((aligned(16))) float Hd[16 * 68];            // this quarter's 64 hidden activations per winner
+    __shared__ __attribute__((aligned(16))) float A[PT_A_FLOATS];         // the 16 winners' patches (point_heads.h)
+    __shared__ __attribute__((aligned(16))) float Hd[PT_HD_FLOATS];       // this quarter's 64 hidden activations per winner
     __shared__ int wy[16], wx[16];
-    constexpr int HCH[CT_NUM_HEADS] = {2, 2, 2, 4, 4, 1, 8, 3, 2, 8, 3};
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int bid = blockIdx.x;
@@ -811,22 +808,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int b = tile / a.tiles, t = tile - b * a.tiles;
     const int HW = a.h * a.w;
     const int hd = a.head[hi];
-    const int cout = HCH[hd];
-    // ---- this wave's weights: 36 (tap, slab) fragments of 1 KiB for n-tile 4 * quarter + wave, all requested now ----
-    const float *wp = a.w1[hi] + ((size_t)(quarter * 4 + wave) << 8) + (lane << 2);
+    const int cout = ct_head_ch(hd);
     f32x4 bq[36];
-#pragma unroll
-    for (int st = 0; st < 36; ++st) bq[st] = *reinterpret_cast<const f32x4 *>(wp + (size_t)st * (16 << 8));
-    const int li = lane & 15, lg = lane >> 4;
-    const float bias1 = a.b1[hi][quarter * 64 + wave * 16 + li];
+    const float bias1 = pt_load_weights(bq, a.w1[hi], a.b1[hi], quarter, wave, lane);      // (requested before the winners are read)
     if (tid < 16) {
         const int r = t * 16 + tid;
         int y = -4, x = -4;
         if (r < a.K) {
-            const unsigned long long k = a.winners[(size_t)b * a.K + r];
-            const unsigned flat = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
-            const int p = (int)(flat % (unsigned)HW);
-            y = p / a.w; x = p - y * a.w;
+            const Winner wn = key_winner(a.winners[(size_t)b * a.K + r], HW, a.w);
+            y = wn.y; x = wn.x;
         }
         wy[tid] = y; wx[tid] = x;
     }
@@ -835,44 +825,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // mirrored pixel -- a second pass over that image's patch at (y, w - 1 - x); every other head reads image b alone
     const int npass = (a.flip_B > 0 && a.flip_mode[hi] != 0) ? 2 : 1;
     for (int pass = 0; pass < npass; ++pass) {
-    // ---- the 16 winners' 3x3 x 64 patches: 16 x 9 x 16 float4 items (rows past K and taps outside the map: zero) ----
-    {
-        const float *fb = a.feat + (size_t)(pass ? a.flip_B + b : b) * a.feat_bs;
-        f32x4 pv[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int it = tid + 256 * j;
-            const int m = it / 144, rem = it - m * 144;
-            const int tap = rem >> 4, q = rem & 15;
-            const int cx = pass ? a.w - 1 - wx[m] : wx[m];
-            const int y = wy[m] + tap / 3 - 1, x = cx + tap % 3 - 1;
-            const bool ok = y >= 0 && y < a.h && x >= 0 && x < a.w && wy[m] >= 0;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(fb + (ok ? ((size_t)y * a.w + x) * a.ldf + q * 4 : 0));
-            pv[j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        if (pass) __syncthreads();                                // (pass 0's hidden tile / patch reads are done)
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int it = tid + 256 * j;
-            const int m = it / 144, rem = it - m * 144;
-            const int tap = rem >> 4, q = rem & 15;
-            *reinterpret_cast<f32x4 *>(A + (tap * 4 + (q >> 2)) * 256 + m * 16 + (((q & 3) ^ ((m >> 1) & 2)) << 2)) = pv[j];
-        }
-    }
+    // ---- the 16 winners' patches (rows past K: zero); the barrier of pass 1: pass 0's hidden tile / patch reads are done ----
+    pt_gather_patches(A, tid, a.h, a.w, a.ldf, pass != 0, [&](int m, const float *&img, int &y, int &x) {
+        img = a.feat + (size_t)(pass ? a.flip_B + b : b) * a.feat_bs; y = wy[m]; x = pass ? a.w - 1 - wx[m] : wx[m];
+    });
     __syncthreads();
-    {
-        const int aoff = li * 16 + ((lg ^ ((li >> 1) & 2)) << 2);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int st = 0; st < 36; ++st) {
-            const f32x4 af = *reinterpret_cast<const f32x4 *>(A + st * 256 + aoff);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], bq[st][e], acc, 0, 0, 0);
-        }
-        // C layout: row (winner) = lg * 4 + e, column (hidden channel of this quarter) = 16 * wave + li
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Hd[(lg * 4 + e) * 68 + wave * 16 + li] = fmaxf(acc[e] + bias1, 0.0f);
-    }
+    pt_hidden_tile(Hd, A, bq, bias1, wave, lane);
     __syncthreads();
     // ---- this quarter's share of conv1x1 256 -> cout: 2 lanes per (winner, channel), 32 hidden values each ----
     {
@@ -880,8 +838,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int m = pair >> 3, c = pair & 7;
         float sum = 0.f;
         if (c < cout) {
-            const float *w2 = a.w2[hi] + c * SP_HID + quarter * 64 + part * 32;
-            const float *hh = Hd + m * 68 + part * 32;
+            const float *w2 = a.w2[hi] + c * PT_HID + quarter * 64 + part * 32;
+            const float *hh = Hd + m * PT_HD_LD + part * 32;
 #pragma unroll
             for (int j = 0; j < 32; ++j) sum += hh[j] * w2[j];
         }
@@ -897,16 +855,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // workgroup: 536 us per launch.  A kernel boundary is the cheaper way to make the partials visible.)
 __global__ __launch_bounds__(128) void sparse_rows_kernel(SparseArgs a)
 {
-    constexpr int HCH[CT_NUM_HEADS] = {2, 2, 2, 4, 4, 1, 8, 3, 2, 8, 3};
     const int b = blockIdx.x;
     const int HW = a.h * a.w;
     for (int r = threadIdx.x; r < a.K; r += blockDim.x) {
-        const unsigned long long k = a.winners[(size_t)b * a.K + r];
-        const unsigned flat = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
-        const int cls = (int)(flat / (unsigned)HW);
-        const int p = (int)(flat - (unsigned)cls * (unsigned)HW);
-        const int y = p / a.w, x = p - y * a.w;
-        const float score = ord2f((unsigned)(k >> 32));
+        const Winner wn = key_winner(a.winners[(size_t)b * a.K + r], HW, a.w);
         const int tile = b * a.tiles + (r >> 4), m = r & 15;
         float V[CT_NUM_HEADS][8];
 #pragma unroll
@@ -918,7 +870,7 @@ __global__ __launch_bounds__(128) void sparse_rows_kernel(SparseArgs a)
             const bool both = a.flip_B > 0 && a.flip_mode[h2] != 0;
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                if (c >= HCH[hd2]) continue;
+                if (c >= ct_head_ch(hd2)) continue;
                 auto value = [&](int pass) {
                     const float *pp = a.partial + ((((size_t)tile * a.nheads + h2) * 2 + pass) * 4 * 16 + m) * 8 + c;
                     float v = pp[0];                       // quarters summed in order: deterministic
@@ -943,12 +895,10 @@ __global__ __launch_bounds__(128) void sparse_rows_kernel(SparseArgs a)
         }
         float *row = a.out + ((size_t)b * a.K + r) * a.F;
         float *hrow = a.host_out ? a.host_out + ((size_t)b * a.K + r) * a.F : nullptr;
-        emit_row(row, hrow, a.present, score, cls, (float)x, (float)y, [&](int hd3, int ch) { return V[hd3][ch]; });
+        emit_row(row, hrow, a.present, wn.score, wn.cls, (float)wn.x, (float)wn.y, [&](int hd3, int ch) { return V[hd3][ch]; });
     }
     if (a.done_flag) raise_done_flag(a.done_flag, a.done_counter, a.B);
 }
-
-const int kHeadCh[CT_NUM_HEADS] = {2, 2, 2, 4, 4, 1, 8, 3, 2, 8, 3};
 
 int check(const ct_decode_desc *d, const char *who)
 {
@@ -960,14 +910,14 @@ int check(const ct_decode_desc *d, const char *who)
     // the sparse-heads descriptor is validated HERE, for every entry point that reads it (ct_decode_workspace_bytes sizes the
     // workspace from nheads, ct_decode_row_floats walks head[]: a bad descriptor must be an error, not a wrapped size)
     if (const ct_sparse_heads_desc *sp = d->sparse) {
-        if (sp->nheads < 1 || sp->nheads > CT_NUM_HEADS || !sp->feat || sp->ldf < 64 || (sp->ldf & 3) || ((uintptr_t)sp->feat & 15))
-            CT_FAIL_ARG("%s: sparse heads need 1..%d heads and a 16-byte aligned NHWC feature view of >= 64 channels", who, CT_NUM_HEADS);
+        if (sp->nheads < 1 || sp->nheads > CT_NUM_HEADS) CT_FAIL_ARG("%s: sparse nheads=%d out of range (1..%d)", who, sp->nheads, CT_NUM_HEADS);
+        const int rc = ct_check_sparse_feat(who, sp->feat, sp->ldf, sp->flip_B, d->B);
+        if (rc != CT_OK) return rc;
         for (int i = 0; i < sp->nheads; ++i) {
-            if (sp->head[i] < 0 || sp->head[i] >= CT_NUM_HEADS || !sp->w1[i] || !sp->b1[i] || !sp->w2[i] || !sp->b2[i])
+            if (sp->head[i] < 0 || sp->head[i] >= CT_NUM_HEADS || !ct_sparse_head_ok(sp->w1[i], sp->b1[i], sp->w2[i], sp->b2[i], false))
                 CT_FAIL_ARG("%s: sparse head %d is incomplete", who, i);
             if (d->heads[sp->head[i]]) CT_FAIL_ARG("%s: head %d is both dense and sparse", who, sp->head[i]);
         }
-        if (sp->flip_B < 0 || (sp->flip_B > 0 && sp->flip_B != d->B)) CT_FAIL_ARG("%s: sparse flip_B must be 0 or B (feat then holds 2 * B images)", who);
     }
     return CT_OK;
 }
@@ -1001,7 +951,7 @@ extern "C" int ct_decode_row_floats(const ct_decode_desc *d)
     const int rest[7] = {CT_HEAD_TRACKING, CT_HEAD_DEP, CT_HEAD_ROT, CT_HEAD_DIM, CT_HEAD_AMODEL_OFFSET,
                          CT_HEAD_NUSCENES_ATT, CT_HEAD_VELOCITY};
     for (int q = 0; q < 7; ++q)
-        if (has(rest[q])) f += kHeadCh[rest[q]];
+        if (has(rest[q])) f += ct_head_ch(rest[q]);
     return f;
 }
 
@@ -1081,8 +1031,8 @@ extern "C" int ct_decode(const ct_decode_desc *d, void *stream)
     Stage2Args a2;
     a2.cand = a1.cand; a2.hm = d->hm;
     for (int i = 0; i < CT_NUM_HEADS; ++i) {
-        a2.heads[i] = d->heads[i]; a2.head_ch[i] = kHeadCh[i];
-        a2.head_bs[i] = d->head_batch_stride[i] ? (size_t)d->head_batch_stride[i] : (size_t)kHeadCh[i] * HWs;
+        a2.heads[i] = d->heads[i];
+        a2.head_bs[i] = d->head_batch_stride[i] ? (size_t)d->head_batch_stride[i] : (size_t)ct_head_ch(i) * HWs;
     }
     a2.hm_bs = a1.hm_bs;
     a2.out = d->out; a2.inds = (long long *)d->inds;

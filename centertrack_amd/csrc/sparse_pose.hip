@@ -5,12 +5,12 @@
 //   1. the joint decode of ct_decode_pose, unchanged (csrc/pose.hip: hm_hp as B*J one-class images through ct_decode);
 //   2. point_eval_kernel: conv3x3 64 -> 256 + bias + ReLU + conv1x1 256 -> c of a head at a LIST of points -- up to three
 //      lists in one launch: hps at the winners of image b, hps at their mirrored pixels in image flip_B + b (flip_test),
-//      the offset head at the joint peaks.  The contraction is sparse_heads_kernel's (csrc/decode.hip): one workgroup =
-//      16 points x one quarter of the 256 hidden channels, a [16 x 576] x [576 x 64] product on mfma_f32_16x16x4f32 with
-//      the wave's weights requested before the points are read.  What is new is the tail: any c <= 64 output channels
-//      (hps has 2J = 34), the quarter's slice of the 1x1 weights staged in LDS, partials laid out [quarter][point][c].
-//      A point's value depends on its pixel alone, not on its place in a tile or in the launch: every row of the MFMA tile
-//      is the same k-ordered fma chain and every (point, channel) of the tail the same 64-term sum;
+//      the offset head at the joint peaks.  The contraction is the shared core of csrc/point_heads.h, which
+//      sparse_heads_kernel (csrc/decode.hip) calls too: one workgroup = 16 points x one quarter of the 256 hidden channels,
+//      the wave's weights requested before the points are read.  The kernel's own part is the tail: any c <= 64 output
+//      channels (hps has 2J = 34), the quarter's slice of the 1x1 weights staged in LDS, partials laid out
+//      [quarter][point][c].  A point's value depends on its pixel alone, not on its place in a tile or in the launch: every
+//      row of the MFMA tile is the same k-ordered fma chain and every (point, channel) of the tail the same 64-term sum;
 //   3. pose_values_kernel: the four quarters summed in order (no atomics), + bias, and for hps under flip_test the merge of
 //      ct_flip_merge's CT_FLIP_JOINT_OFFSETS at the point: (a + s * b) / 2 with b the partner joint's pair of the mirrored
 //      image, x negated -> compact hps [B*K][2J] and offsets [B*J*K][2];
@@ -20,10 +20,10 @@
 #include <stdint.h>
 
 #include "ct_common.h"
+#include "point_heads.h"
 
 namespace {
 
-constexpr int PT_HID = 256;          // hidden channels of a head (head_conv)
 constexpr int PT_MAX_C = 64;         // output channels of the widest head the tail takes
 constexpr int PT_MAX_JOBS = 3;
 constexpr int PT_MAX_JOINTS = 32;
@@ -43,8 +43,8 @@ struct PtArgs {
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void point_eval_kernel(PtArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float A[36 * 256];            // [tap * 4 + slab][16 points][16 ch], swizzled
-    __shared__ __attribute__((aligned(16))) float Hd[16 * 68];            // this quarter's 64 hidden activations per point
+    __shared__ __attribute__((aligned(16))) float A[PT_A_FLOATS];         // the 16 points' patches (point_heads.h)
+    __shared__ __attribute__((aligned(16))) float Hd[PT_HD_FLOATS];       // this quarter's 64 hidden activations per point
     __shared__ float W2[PT_MAX_C * 65];                                   // this quarter's [c][64] slice of the 1x1 weights
     __shared__ int wy[16], wx[16], wi[16];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -57,13 +57,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const PtJob &jb = a.job[ji];
     const int r0 = (tile - jb.tile0) * 16;
     const int HW = a.h * a.w;
-    // ---- this wave's weights: 36 (tap, slab) fragments of 1 KiB for n-tile 4 * quarter + wave, all requested now ----
-    const float *wp = jb.w1 + ((size_t)(quarter * 4 + wave) << 8) + (lane << 2);
     f32x4 bq[36];
-#pragma unroll
-    for (int st = 0; st < 36; ++st) bq[st] = *reinterpret_cast<const f32x4 *>(wp + (size_t)st * (16 << 8));
-    const int li = lane & 15, lg = lane >> 4;
-    const float bias1 = jb.b1[quarter * 64 + wave * 16 + li];
+    const float bias1 = pt_load_weights(bq, jb.w1, jb.b1, quarter, wave, lane);            // (requested before the points are read)
     const int cout = jb.c;
     for (int i = tid; i < cout * 64; i += 256) W2[(i >> 6) * 65 + (i & 63)] = jb.w2[(size_t)(i >> 6) * PT_HID + quarter * 64 + (i & 63)];
     if (tid < 16) {
@@ -80,47 +75,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         wy[tid] = y; wx[tid] = x; wi[tid] = img;
     }
     __syncthreads();
-    // ---- the 16 points' 3x3 x 64 patches: 16 x 9 x 16 float4 items (rows past P and taps outside the map: zero) ----
-    {
-        f32x4 pv[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int it = tid + 256 * j;
-            const int m = it / 144, rem = it - m * 144;
-            const int tap = rem >> 4, q = rem & 15;
-            const int y = wy[m] + tap / 3 - 1, x = wx[m] + tap % 3 - 1;
-            const bool ok = y >= 0 && y < a.h && x >= 0 && x < a.w && wy[m] >= 0;
-            const float *fb = a.feat + (size_t)wi[m] * a.feat_bs;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(fb + (ok ? ((size_t)y * a.w + x) * a.ldf + q * 4 : 0));
-            pv[j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int it = tid + 256 * j;
-            const int m = it / 144, rem = it - m * 144;
-            const int tap = rem >> 4, q = rem & 15;
-            *reinterpret_cast<f32x4 *>(A + (tap * 4 + (q >> 2)) * 256 + m * 16 + (((q & 3) ^ ((m >> 1) & 2)) << 2)) = pv[j];
-        }
-    }
+    // ---- the 16 points' patches (rows past P: zero), each from its own image, the mirror already in wx ----
+    pt_gather_patches(A, tid, a.h, a.w, a.ldf, false, [&](int m, const float *&img, int &y, int &x) {
+        img = a.feat + (size_t)wi[m] * a.feat_bs; y = wy[m]; x = wx[m];
+    });
     __syncthreads();
-    {
-        const int aoff = li * 16 + ((lg ^ ((li >> 1) & 2)) << 2);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int st = 0; st < 36; ++st) {
-            const f32x4 af = *reinterpret_cast<const f32x4 *>(A + st * 256 + aoff);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], bq[st][e], acc, 0, 0, 0);
-        }
-        // C layout: row (point) = lg * 4 + e, column (hidden channel of this quarter) = 16 * wave + li
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Hd[(lg * 4 + e) * 68 + wave * 16 + li] = fmaxf(acc[e] + bias1, 0.0f);
-    }
+    pt_hidden_tile(Hd, A, bq, bias1, wave, lane);
     __syncthreads();
     // ---- this quarter's share of conv1x1 256 -> c: one lane per (point, channel), its 64 hidden values in order ----
     for (int o = tid; o < 16 * cout; o += 256) {
         const int m = o / cout, c = o - m * cout;
-        const float *hh = Hd + m * 68, *ww = W2 + c * 65;
+        const float *hh = Hd + m * PT_HD_LD, *ww = W2 + c * 65;
         float sum = 0.f;
 #pragma unroll 16
         for (int j = 0; j < 64; ++j) sum += hh[j] * ww[j];
@@ -179,12 +144,11 @@ int check(const ct_pose_sparse_desc *d, const char *who)
     int rc = ct_pose_check(b, who, 1);
     if (rc != CT_OK) return rc;
     if (b->num_joints < 1 || b->num_joints > PT_MAX_JOINTS) CT_FAIL_ARG("%s: num_joints=%d out of range (1..%d)", who, b->num_joints, PT_MAX_JOINTS);
-    if (!d->feat || ((uintptr_t)d->feat & 15) || d->ldf < 64 || (d->ldf & 3))
-        CT_FAIL_ARG("%s: needs a 16-byte aligned NHWC feature view of >= 64 channels (pitch a multiple of 4)", who);
-    if (!d->hps_w1 || !d->hps_b1 || !d->hps_w2 || !d->hps_b2) CT_FAIL_ARG("%s: the hps head is incomplete", who);
-    const int noff = !!d->off_w1 + !!d->off_b1 + !!d->off_w2 + !!d->off_b2;
-    if (noff != 0 && noff != 4) CT_FAIL_ARG("%s: the offset head is incomplete (all four pointers, or none for +0.5)", who);
-    if (d->flip_B < 0 || (d->flip_B > 0 && d->flip_B != b->B)) CT_FAIL_ARG("%s: flip_B must be 0 or B (feat then holds 2 * B images)", who);
+    rc = ct_check_sparse_feat(who, d->feat, d->ldf, d->flip_B, b->B);
+    if (rc != CT_OK) return rc;
+    if (!ct_sparse_head_ok(d->hps_w1, d->hps_b1, d->hps_w2, d->hps_b2, false)) CT_FAIL_ARG("%s: the hps head is incomplete", who);
+    if (!ct_sparse_head_ok(d->off_w1, d->off_b1, d->off_w2, d->off_b2, true))
+        CT_FAIL_ARG("%s: the offset head is incomplete (all four pointers, or none for +0.5)", who);
     if (d->flip_B > 0) {
         if (!d->flip_pairs || d->num_pairs < 0) CT_FAIL_ARG("%s: flip_B needs flip_pairs (num_pairs may be 0)", who);
         for (int k = 0; k < 2 * d->num_pairs; ++k)

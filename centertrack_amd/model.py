@@ -226,6 +226,16 @@ class DLASegHIP(torch.nn.Module):
         self._prepared = P
         return P
 
+    def _winner_heads(self, P, feat):
+        """``plan['sparse']``: the regression heads ct_decode evaluates at the K winners (ct_sparse_heads_desc), None if there
+        are none.  Dead heads are left out: generic_decode overwrites the wh box with the ltrb / ltrb_amodal box
+        (decode.py:131-139,150-159) and `reg` only feeds the wh box (decode.py:102-110) -- neither reaches the returned dict,
+        so with the MOT head set (opts.py:343-359 + --ltrb_amodal) they are not evaluated at all"""
+        sp = [h for h in self.heads if h in _lib.HEAD_INDEX and ('sparse.' + h) in P]
+        if {'ltrb', 'ltrb_amodal'} & set(self.heads):
+            sp = [h for h in sp if h not in ('reg', 'wh')]
+        return {'feat': feat, 'heads': [(h,) + P['sparse.' + h] for h in sp], 'depth_scale': self.depth_scale} if sp else None
+
     def _build_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads=False, sparse_pose=False, *, trunk_only=False):
         """``sparse_pose`` (opt-in, pose head sets): hm and hm_hp are the only dense head launches; reg / wh or ltrb / tracking
         go to ``plan['sparse']`` like ``sparse_heads``, hps and the offset head to ``plan['sparse_pose']``.
@@ -377,27 +387,17 @@ class DLASegHIP(torch.nn.Module):
                     or 'hm' not in small or 'hm_hp' not in big):
                 raise _lib.CTError('sparse pose heads need hm, hps and hm_hp heads with head_conv 256, no ltrb_amodal head '
                                    '(the match finds its gate box in the packed row) and the detector\'s fused epilogues')
-            sp = [h for h in self.heads if h in _lib.HEAD_INDEX and ('sparse.' + h) in P]
-            if 'ltrb' in hs:                                    # (dead heads, as below)
-                sp = [h for h in sp if h not in ('reg', 'wh')]
-            if sp:
-                plan['sparse'] = {'feat': feat, 'heads': [(h,) + P['sparse.' + h] for h in sp], 'depth_scale': self.depth_scale}
+            plan['sparse'] = self._winner_heads(P, feat)
             off = 'hp_offset' if 'hp_offset' in hs else 'reg' if 'reg' in hs else None
             plan['sparse_pose'] = {'feat': feat, 'hps': P['sparse.hps'], 'off': P['sparse.' + off] if off else None}
             small, big = ['hm'], ['hm_hp']
         if sparse_heads:
             # opt-in (detector only, never Module.forward): the regression heads the decode reads at the K winners are not
             # computed as maps -- ct_decode evaluates them at those pixels (ct_sparse_heads_desc)
-            sp = [h for h in self.heads if h in _lib.HEAD_INDEX and ('sparse.' + h) in P]
-            if {'ltrb', 'ltrb_amodal'} & set(self.heads):
-                # dead heads: generic_decode overwrites the wh box with the ltrb / ltrb_amodal box (decode.py:131-139,150-159)
-                # and `reg` only feeds the wh box (decode.py:102-110) -- neither reaches the returned dict, so with the
-                # MOT head set (opts.py:343-359 + --ltrb_amodal) they are not evaluated at all
-                sp = [h for h in sp if h not in ('reg', 'wh')]
-            if not sp or 'hm' not in self.heads or {'hps', 'hm_hp'} & set(self.heads) or not fuse_sigmoid:
+            plan['sparse'] = self._winner_heads(P, feat)
+            if plan['sparse'] is None or 'hm' not in self.heads or {'hps', 'hm_hp'} & set(self.heads) or not fuse_sigmoid:
                 raise _lib.CTError('sparse heads need an hm head, regression heads with head_conv 256, no pose heads '
                                    'and the detector\'s fused epilogues')
-            plan['sparse'] = {'feat': feat, 'heads': [(h,) + P['sparse.' + h] for h in sp], 'depth_scale': self.depth_scale}
             small = [h for h in small if not (h in _lib.HEAD_INDEX and ('sparse.' + h) in P)]          # (the dead heads leave the dense launch too)
             if any(h in _lib.HEAD_INDEX and ('sparse.' + h) in P for h in big):          # (more small heads than one fused launch holds: not with sparse heads)
                 raise _lib.CTError('sparse heads: %s do not fit the fused-heads launch' % [h for h in big if ('sparse.' + h) in P])

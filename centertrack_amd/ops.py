@@ -881,6 +881,21 @@ def decode_layout(head_names):
     return lay, f
 
 
+def _planes_ok(t, h, w):      # every image's [c,h,w] block contiguous; images may be strided (channel slices)
+    return t.stride(3) == 1 and t.stride(2) == w and (t.shape[1] == 1 or t.stride(1) == h * w)
+
+
+def _sparse_feat(spec, B, h, w):      # -> (pointer, pitch, flip_B) of the sparse heads' feature view; flip_test: 2 * B images
+    feat, flip = spec['feat'], bool(spec.get('flip'))
+    assert feat.C == 64 and (feat.N, feat.H, feat.W) == ((2 * B if flip else B), h, w)
+    return feat.ptr, feat.ld, B if flip else 0
+
+
+def _head_ptrs(w1, b1, w2, b2, c):      # a sparse head of c channels: packed conv3x3 weight, hidden bias [256], w2 [c,256], b2 [c]
+    assert tuple(w2.shape) == (c, 256) and w2.is_contiguous() and b1.numel() == 256 and b2.numel() == c
+    return w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+
+
 class Decoder(object):
     """Pre-built ct_decode call (+ ct_decode_pose when the pose heads ``hps`` / ``hm_hp`` are given) for fixed
     shapes (graph-capture friendly).  One packed buffer ``out`` [B,K,F]: the rows of ct_decode followed, for the
@@ -913,56 +928,20 @@ class Decoder(object):
         self.K = K
         B, C, h, w = hm.shape
         self.hm, self.heads = hm, dict(heads)
-
-        def planes_ok(t):      # every image's [c,h,w] block contiguous; images may be strided (channel slices)
-            return t.stride(3) == 1 and t.stride(2) == w and (t.shape[1] == 1 or t.stride(1) == h * w)
-        d = DecodeDesc()
-        assert planes_ok(hm)
-        d.hm, d.B, d.C, d.h, d.w, d.K = hm.data_ptr(), B, C, h, w, K
-        d.hm_batch_stride = hm.stride(0)
-        for name, t in heads.items():
-            if name in _lib.HEAD_INDEX:
-                assert planes_ok(t) and t.shape[1] == _lib.HEAD_CH[name], name
-                d.heads[_lib.HEAD_INDEX[name]] = t.data_ptr()
-                d.head_batch_stride[_lib.HEAD_INDEX[name]] = t.stride(0)
+        sparse_names = [n for n, *_ in sparse['heads']] if sparse is not None else []
+        d = self._dense_desc(hm, heads, K)
         self.sparse = None
         if sparse is not None:
-            assert 'hps' not in heads and all(n not in heads for n, *_ in sparse['heads'])
-            sp = _lib.SparseHeadsDesc()
-            feat = sparse['feat']
-            flip = bool(sparse.get('flip'))
-            assert feat.C == 64 and (feat.N, feat.H, feat.W) == ((2 * B if flip else B), h, w)
-            sp.flip_B = B if flip else 0
-            sp.feat, sp.ldf, sp.nheads = feat.ptr, feat.ld, len(sparse['heads'])
-            for i, (name, w1, b1, w2, b2) in enumerate(sparse['heads']):
-                assert tuple(w2.shape) == (_lib.HEAD_CH[name], 256) and w2.is_contiguous() and b1.numel() == 256
-                sp.head[i] = _lib.HEAD_INDEX[name]
-                sp.flip_mode[i] = (1 if name in ('wh', 'dep', 'dim') else 2 if name == 'amodel_offset' else 0) if flip else 0
-                sp.w1[i], sp.b1[i], sp.w2[i], sp.b2[i] = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
-            sp.depth_scale = float(sparse.get('depth_scale', 1.0))
-            sp.zero_tracking = int(bool(sparse.get('zero_tracking', False)))
-            self.sparse = (sp, sparse)                     # (keeps the tensors alive)
-            d.sparse = ctypes.pointer(sp)
-        self.layout, self.F = decode_layout([n for n in heads if n in _lib.HEAD_INDEX] +
-                                            ([n for n, *_ in sparse['heads']] if sparse is not None else []))
-        F0 = self.F
+            assert 'hps' not in heads and all(n not in heads for n in sparse_names)
+            self.sparse = (self._sparse_heads_desc(sparse, B, h, w), sparse)      # (keeps the tensors alive)
+            d.sparse = ctypes.pointer(self.sparse[0])
+        self.layout, F0 = decode_layout([n for n in heads if n in _lib.HEAD_INDEX] + sparse_names)
         assert lib.ct_decode_row_floats(ctypes.byref(d)) == F0
-        self.pose = self.pose_sparse = None
-        if sparse_pose is not None:
-            if 'hps' in heads or 'hp_offset' in heads or 'hm_hp' not in heads:
-                raise _lib.CTError('sparse pose heads: `heads` holds hm_hp and neither hps nor hp_offset')
-            if sparse is not None and 'ltrb_amodal' in [n for n, *_ in sparse['heads']]:
-                raise _lib.CTError('sparse pose heads beside a sparse ltrb_amodal head: the rows do not hold the gate box')
-            J = heads['hm_hp'].shape[1]
+        J = self._pose_joints(heads, sparse_names, sparse_pose)
+        self.F = F0
+        if J is not None:
             self.layout = self.layout + [('hps', F0, 2 * J), ('kps_score', F0 + 2 * J, 1)]
             self.F = F0 + 2 * J + 1
-        if 'hps' in heads:                                 # pose branch, decode.py:161-171
-            J = heads['hps'].shape[1] // 2
-            if 'hm_hp' in heads:
-                self.layout = self.layout + [('hps', F0, 2 * J), ('kps_score', F0 + 2 * J, 1)]
-                self.F = F0 + 2 * J + 1
-            else:                                          # decode.py:80-81: no refinement, kps_score = kps
-                raise _lib.CTError('the pose branch without an hm_hp head is not implemented')
         self.out = torch.empty((B, K, self.F), dtype=torch.float32, device=hm.device)
         self.inds = torch.empty((B, K), dtype=torch.int64, device=hm.device)
         nbytes = lib.ct_decode_workspace_bytes(ctypes.byref(d))
@@ -975,73 +954,118 @@ class Decoder(object):
         d.out_stride = self.F
         d.workspace, d.workspace_bytes = self.ws.data_ptr(), nbytes
         self.direct = False
-        if host_out is not None and done_flag is not None and 'hps' not in heads and sparse_pose is None:
+        if host_out is not None and done_flag is not None and J is None:
             assert tuple(host_out.shape) == (B, K, self.F) and host_out.is_pinned() and done_flag.is_pinned()
             self.done_counter = torch.zeros((4,), dtype=torch.int32, device=hm.device)
             d.host_out, d.done_flag = host_out.data_ptr(), done_flag.data_ptr()
             d.done_counter = self.done_counter.data_ptr()
             self.direct = True
         self.desc = d
-        if 'hps' in heads or sparse_pose is not None:
-            hm_hp = heads['hm_hp']
-            assert hm_hp.is_contiguous() and hm_hp.shape[1] == J
-            if sparse_pose is not None:
-                hps = off = None
-                spd = _lib.PoseSparseDesc()
-                pd = spd.base
-            else:
-                hps = heads['hps']
-                off = heads.get('hp_offset', heads.get('reg'))
-                assert planes_ok(hps) and (off is None or planes_ok(off))
-                pd = _lib.PoseDesc()
-            pd.rows, pd.row_floats, pd.inds = self.out.data_ptr(), self.F, self.inds.data_ptr()
-            # the gate box of _update_kps_with_hm is generic_decode's local `bboxes`: wh, overridden by ltrb -- never the
-            # ltrb_amodal box that replaces ret['bboxes'] in the packed row (decode.py:123,137 vs 159)
-            # (sparse main heads: the rows are the only place the box is -- column 4, or the box-less variant)
-            in_rows = set(heads) | set(n for n, *_ in sparse['heads']) if sparse is not None else set(heads)
-            if 'ltrb_amodal' in in_rows or not ({'wh', 'ltrb'} & in_rows):
-                pd.box_col = -1
-                for name, fld in (('wh', 'box_wh'), ('ltrb', 'box_ltrb')):
-                    if name in heads:
-                        assert planes_ok(heads[name])
-                        setattr(pd, fld, heads[name].data_ptr())
-                        setattr(pd, fld + '_batch_stride', heads[name].stride(0))
-                if 'wh' in heads and 'reg' in heads:
-                    pd.box_reg, pd.box_reg_batch_stride = heads['reg'].data_ptr(), heads['reg'].stride(0)
-            else:
-                pd.box_col = 4
-            pd.B, pd.h, pd.w, pd.K, pd.num_joints = B, h, w, K, J
-            pd.hps, pd.hm_hp, pd.hp_offset = _p(hps), hm_hp.data_ptr(), _p(off)
-            pd.hps_batch_stride = hps.stride(0) if hps is not None else 0
-            pd.hp_offset_batch_stride = off.stride(0) if off is not None else 0
-            pd.out, pd.out_stride = self.out.data_ptr() + 4 * F0, self.F
-            if sparse_pose is not None:
-                feat, flip = sparse_pose['feat'], bool(sparse_pose.get('flip'))
-                assert feat.C == 64 and (feat.N, feat.H, feat.W) == ((2 * B if flip else B), h, w)
-                spd.feat, spd.ldf, spd.flip_B = feat.ptr, feat.ld, B if flip else 0
-                for pre, c, wts in (('hps', 2 * J, sparse_pose['hps']), ('off', 2, sparse_pose.get('off'))):
-                    if wts is not None:
-                        w1, b1, w2, b2 = wts
-                        assert tuple(w2.shape) == (c, 256) and w2.is_contiguous() and b1.numel() == 256 and b2.numel() == c
-                        for fld, t in zip(('w1', 'b1', 'w2', 'b2'), wts):
-                            setattr(spd, '%s_%s' % (pre, fld), t.data_ptr())
-                pairs = np.ascontiguousarray(sparse_pose.get('flip_pairs', ()), np.int32).reshape(-1, 2)
-                spd.flip_pairs, spd.num_pairs = pairs.ctypes.data, len(pairs)
-                need = ctypes.c_size_t(0)
-                _lib.check(lib.ct_decode_pose_sparse_workspace_bytes(ctypes.byref(spd), ctypes.byref(need)),
-                           'ct_decode_pose_sparse_workspace_bytes')
-                # (zeroed only so that the offsets area reads as 0 without an offset head: the call neither writes nor reads it
-                #  then, and of everything else it reads nothing it has not written)
-                self.pose_ws = torch.zeros(need.value // 8 + 1, dtype=torch.int64, device=hm.device)
-                pd.workspace, pd.workspace_bytes = self.pose_ws.data_ptr(), self.pose_ws.numel() * 8
-                self.pose_sparse = (spd, sparse_pose, pairs)            # (keeps the tensors and the pairs alive)
-                return
+        self.pose = self.pose_sparse = None
+        if J is not None and sparse_pose is None:
+            pd = _lib.PoseDesc()
+            self._fill_pose_desc(pd, heads, sparse_names, J, F0, heads['hps'], heads.get('hp_offset', heads.get('reg')))
             pbytes = lib.ct_decode_pose_workspace_bytes(ctypes.byref(pd))
             if pbytes == 0:
                 _lib.check(1, 'ct_decode_pose_workspace_bytes')
             self.pose_ws = torch.empty(pbytes // 8 + 1, dtype=torch.int64, device=hm.device)
             pd.workspace, pd.workspace_bytes = self.pose_ws.data_ptr(), self.pose_ws.numel() * 8
             self.pose = pd
+        elif J is not None:
+            spd = _lib.PoseSparseDesc()
+            self._fill_pose_desc(spd.base, heads, sparse_names, J, F0)
+            pairs = self._fill_pose_sparse_desc(spd, sparse_pose, J)
+            need = ctypes.c_size_t(0)
+            _lib.check(lib.ct_decode_pose_sparse_workspace_bytes(ctypes.byref(spd), ctypes.byref(need)),
+                       'ct_decode_pose_sparse_workspace_bytes')
+            # (zeroed only so that the offsets area reads as 0 without an offset head: the call neither writes nor reads it
+            #  then, and of everything else it reads nothing it has not written)
+            self.pose_ws = torch.zeros(need.value // 8 + 1, dtype=torch.int64, device=hm.device)
+            spd.base.workspace, spd.base.workspace_bytes = self.pose_ws.data_ptr(), self.pose_ws.numel() * 8
+            self.pose_sparse = (spd, sparse_pose, pairs)                # (keeps the tensors and the pairs alive)
+
+    @staticmethod
+    def _dense_desc(hm, heads, K):
+        """the ct_decode descriptor of the heat map and the dense head maps (outputs and workspace are set by the caller)"""
+        B, C, h, w = hm.shape
+        d = DecodeDesc()
+        assert _planes_ok(hm, h, w)
+        d.hm, d.B, d.C, d.h, d.w, d.K = hm.data_ptr(), B, C, h, w, K
+        d.hm_batch_stride = hm.stride(0)
+        for name, t in heads.items():
+            if name in _lib.HEAD_INDEX:
+                assert _planes_ok(t, h, w) and t.shape[1] == _lib.HEAD_CH[name], name
+                d.heads[_lib.HEAD_INDEX[name]] = t.data_ptr()
+                d.head_batch_stride[_lib.HEAD_INDEX[name]] = t.stride(0)
+        return d
+
+    @staticmethod
+    def _sparse_heads_desc(sparse, B, h, w):
+        sp = _lib.SparseHeadsDesc()
+        sp.feat, sp.ldf, sp.flip_B = _sparse_feat(sparse, B, h, w)
+        sp.nheads = len(sparse['heads'])
+        for i, (name, *wts) in enumerate(sparse['heads']):
+            sp.head[i] = _lib.HEAD_INDEX[name]
+            sp.flip_mode[i] = (1 if name in ('wh', 'dep', 'dim') else 2 if name == 'amodel_offset' else 0) if sp.flip_B else 0
+            sp.w1[i], sp.b1[i], sp.w2[i], sp.b2[i] = _head_ptrs(*wts, _lib.HEAD_CH[name])
+        sp.depth_scale = float(sparse.get('depth_scale', 1.0))
+        sp.zero_tracking = int(bool(sparse.get('zero_tracking', False)))
+        return sp
+
+    @staticmethod
+    def _pose_joints(heads, sparse_names, sparse_pose):
+        """the number of joints of the pose task (decode.py:161-171), None without one"""
+        if sparse_pose is not None:
+            if 'hps' in heads or 'hp_offset' in heads or 'hm_hp' not in heads:
+                raise _lib.CTError('sparse pose heads: `heads` holds hm_hp and neither hps nor hp_offset')
+            if 'ltrb_amodal' in sparse_names:
+                raise _lib.CTError('sparse pose heads beside a sparse ltrb_amodal head: the rows do not hold the gate box')
+            return heads['hm_hp'].shape[1]
+        if 'hps' not in heads:
+            return None
+        if 'hm_hp' not in heads:                           # decode.py:80-81: no refinement, kps_score = kps
+            raise _lib.CTError('the pose branch without an hm_hp head is not implemented')
+        return heads['hps'].shape[1] // 2
+
+    def _fill_pose_desc(self, pd, heads, sparse_names, J, F0, hps=None, off=None):
+        """what ct_decode_pose and ct_decode_pose_sparse share: the rows, the gate box, the joint heat maps and the output
+        columns; ``hps`` / ``off``: the two maps of the dense form"""
+        (B, _, h, w), K = self.hm.shape, self.K
+        hm_hp = heads['hm_hp']
+        assert hm_hp.is_contiguous() and hm_hp.shape[1] == J and all(t is None or _planes_ok(t, h, w) for t in (hps, off))
+        pd.rows, pd.row_floats, pd.inds = self.out.data_ptr(), self.F, self.inds.data_ptr()
+        # the gate box of _update_kps_with_hm is generic_decode's local `bboxes`: wh, overridden by ltrb -- never the
+        # ltrb_amodal box that replaces ret['bboxes'] in the packed row (decode.py:123,137 vs 159)
+        # (sparse main heads: the rows are the only place the box is -- column 4, or the box-less variant)
+        in_rows = set(heads) | set(sparse_names)
+        if 'ltrb_amodal' in in_rows or not ({'wh', 'ltrb'} & in_rows):
+            pd.box_col = -1
+            for name, fld in (('wh', 'box_wh'), ('ltrb', 'box_ltrb')):
+                if name in heads:
+                    assert _planes_ok(heads[name], h, w)
+                    setattr(pd, fld, heads[name].data_ptr())
+                    setattr(pd, fld + '_batch_stride', heads[name].stride(0))
+            if 'wh' in heads and 'reg' in heads:
+                pd.box_reg, pd.box_reg_batch_stride = heads['reg'].data_ptr(), heads['reg'].stride(0)
+        else:
+            pd.box_col = 4
+        pd.B, pd.h, pd.w, pd.K, pd.num_joints = B, h, w, K, J
+        pd.hps, pd.hm_hp, pd.hp_offset = _p(hps), hm_hp.data_ptr(), _p(off)
+        pd.hps_batch_stride = hps.stride(0) if hps is not None else 0
+        pd.hp_offset_batch_stride = off.stride(0) if off is not None else 0
+        pd.out, pd.out_stride = self.out.data_ptr() + 4 * F0, self.F
+
+    @staticmethod
+    def _fill_pose_sparse_desc(spd, sparse_pose, J):
+        """the feature view, the two heads' weights and the flip pairs behind ``spd.base``; returns the pairs array"""
+        spd.feat, spd.ldf, spd.flip_B = _sparse_feat(sparse_pose, spd.base.B, spd.base.h, spd.base.w)
+        for pre, c, wts in (('hps', 2 * J, sparse_pose['hps']), ('off', 2, sparse_pose.get('off'))):
+            if wts is not None:
+                for fld, ptr in zip(('w1', 'b1', 'w2', 'b2'), _head_ptrs(*wts, c)):
+                    setattr(spd, '%s_%s' % (pre, fld), ptr)
+        pairs = np.ascontiguousarray(sparse_pose.get('flip_pairs', ()), np.int32).reshape(-1, 2)
+        spd.flip_pairs, spd.num_pairs = pairs.ctypes.data, len(pairs)
+        return pairs
 
     def run(self):
         _lib.check(_lib.load().ct_decode(ctypes.byref(self.desc), _lib.stream_ptr()), 'ct_decode')
