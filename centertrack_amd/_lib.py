@@ -320,6 +320,23 @@ class InputsDesc(ctypes.Structure):
                 ('partials', ctypes.c_void_p), ('gs_mean', ctypes.c_void_p)]
 
 
+CT_PIX_BGR24, CT_PIX_RGB24, CT_PIX_NV12, CT_PIX_I420 = range(4)
+CT_FRAMES_MAX = 1024
+
+
+class FrameDesc(ctypes.Structure):
+    _fields_ = [('plane', ctypes.c_void_p * 3), ('pitch', ctypes.c_int * 3),
+                ('format', ctypes.c_int), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('coef', ctypes.c_int * 5), ('reserved', ctypes.c_int),
+                ('M', ctypes.c_double * 6), ('out', ctypes.c_void_p), ('out_flip', ctypes.c_void_p)]
+
+
+class FramesDesc(ctypes.Structure):
+    _fields_ = [('staging_host', ctypes.c_void_p), ('staging_dev', ctypes.c_void_p),
+                ('n', ctypes.c_int), ('dst_w', ctypes.c_int), ('dst_h', ctypes.c_int),
+                ('lut', ctypes.c_void_p)]
+
+
 CT_OPTIM_ADAM, CT_OPTIM_SGD = range(2)
 CT_OPTIM_CHUNK = 4096
 CT_OPTIM_REC_BYTES = 128
@@ -359,7 +376,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_tracker_create', 'ct_tracker_destroy', 'ct_tracker_reset', 'ct_tracker_num_tracks',
            'ct_tracker_id_count', 'ct_tracker_get_tracks', 'ct_tracker_step', 'ct_tracker_prehm_params', 'ct_linear_assignment', 'ct_tracker_set_mode', 'ct_tracker_init_tracks',
            'ct_tracker_step_public', 'ct_tracker_step_dets', 'ct_transform_points',
-           'ct_preprocess_image', 'ct_preprocess_lut', 'ct_preprocess_device', 'ct_graph_begin', 'ct_graph_end', 'ct_graph_launch', 'ct_graph_destroy',
+           'ct_preprocess_image', 'ct_preprocess_lut', 'ct_preprocess_device', 'ct_preprocess_frames', 'ct_graph_begin', 'ct_graph_end', 'ct_graph_launch', 'ct_graph_destroy',
            'ct_memcpy_async', 'ct_memset_async', 'ct_stream_synchronize', 'ct_flip_merge', 'ct_flip_images',
            'ct_frame_loop_create', 'ct_frame_loop_destroy', 'ct_frame_loop_submit', 'ct_frame_loop_wait', 'ct_frame_loop_finish',
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
@@ -491,6 +508,7 @@ def load():
     lib.ct_preprocess_image.argtypes = [p, i, i, i, i, p, i, i, p, p, p, i]
     lib.ct_preprocess_lut.argtypes = [p, p, i, p]
     lib.ct_preprocess_device.argtypes = [p, i, i, i, i, p, i, i, p, p, p, p]
+    lib.ct_preprocess_frames.argtypes = [ctypes.POINTER(FramesDesc), p]
     lib.ct_graph_begin.argtypes = [p]
     lib.ct_graph_end.restype = p
     lib.ct_graph_end.argtypes = [p]

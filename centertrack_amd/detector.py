@@ -33,6 +33,7 @@ NATIVE_LOOP = os.environ.get('CENTERTRACK_NATIVE_LOOP', '1') != '0'   # (A/B swi
 SPLIT_STEM_MAX = int(os.environ.get('CENTERTRACK_SPLIT_STEM_MAX', '0'))
 HOST_FLAG = os.environ.get('CENTERTRACK_HOST_FLAG', '1') != '0'       # end-of-frame flag in pinned host memory (A/B switch)
 HOST_ROWS = os.environ.get('CENTERTRACK_HOST_ROWS', '1') != '0'       # decode writes the rows to pinned host memory itself
+from .frames import FrameLauncher, FrameStager, VideoFrame
 from .image import (affine_transform, draw_umich_gaussian, gaussian_radius, get_affine_transform, make_meta)
 from .model import create_model, load_model
 from .post_process import generic_post_process
@@ -128,6 +129,27 @@ def _frame_source(images, uploaded, slot):
     if images.dtype == torch.float32 and images.is_contiguous():
         return _lib.CT_FRAME_DEVICE if images.device.type == 'cuda' else _lib.CT_FRAME_HOST
     return _lib.CT_FRAME_IN_PLACE
+
+
+RAW_STAGED, RAW_UPLOAD = 'staged', 'upload now'
+
+
+def _raw_frame_source(frames, staged, slot):
+    """where the bytes of this step's ``VideoFrame``s come from: RAW_STAGED only when every element is the same object that
+    was staged for THIS slot (``staged``: the ``frames.StagedFrames`` of the previous step's ``prefetch``, or None), else
+    RAW_UPLOAD -- the caller forgets a stale staging first"""
+    if (staged is not None and staged.slot == slot and len(staged.frames) == len(frames)
+            and all(a is b for a, b in zip(staged.frames, frames))):
+        return RAW_STAGED
+    return RAW_UPLOAD
+
+
+def _is_video(frames):
+    """is a list of raw frames a list of ``VideoFrame``s (True) or of plain arrays (False); a mixture is refused"""
+    kinds = {isinstance(f, VideoFrame) for f in frames}
+    if len(kinds) > 1:
+        raise _lib.CTError('step(): a list of frames holds VideoFrames or plain arrays, not both')
+    return kinds == {True}
 
 
 class _HipGraph(object):
@@ -479,6 +501,8 @@ class StreamDetector(object):
         _lib.check(_lib.load().ct_preprocess_lut(mean.ctypes.data, std.ctypes.data, 3, lut.ctypes.data), 'ct_preprocess_lut')
         self._lut = torch.from_numpy(lut).to(self.device)
         self._raw_bufs = {}
+        # VideoFrames (frames.py): byte staging with its record of the frames uploaded ahead, descriptors + launch
+        self._stager = self._launcher = self._staged = None
         self._carried = {}         # per stream: extras (3D fields) of tracks kept alive without a detection
         # optional hook: called with the packed device rows [B,K,F] right after the frame was launched (multi-GPU
         # all-gather, parallel.DetectionGatherer).  It may return a CUDA event after which the rows have been read: the
@@ -539,6 +563,47 @@ class StreamDetector(object):
                                             self._lut.data_ptr(), frames[s].data_ptr(),
                                             frames[self.B + s].data_ptr() if self.flip else None, st),
                    'ct_preprocess_device')
+
+    def _forget_staged(self):
+        """VideoFrames staged ahead that will not be consumed as they stand"""
+        staged, self._staged = self._staged, None
+        if staged is not None:
+            self._stager.forget(staged)
+
+    def _stage_video_ahead(self, ns, prefetch):
+        """the BYTES of the next step's VideoFrames, uploaded on the stager's copy stream while this frame runs; their
+        pre-process launch belongs to the next step"""
+        self._forget_staged()
+        if self._stager is None:
+            self._stager = FrameStager(self.device, self.B)
+        self._staged = self._stager.stage(prefetch, ns, True)
+
+    def _video_frames(self, ctx, slot, frames, metas):
+        """a step's VideoFrames into ``ctx.frames[slot]`` on the current stream: the bytes staged ahead or uploaded now, one
+        descriptor upload, ONE ``ct_preprocess_frames`` launch for all streams (and the mirrored copies under flip_test)"""
+        B, (H, W), fr = self.B, ctx.hw, ctx.frames[slot]
+        for m in metas:
+            if (int(m['inp_height']), int(m['inp_width'])) != (H, W):
+                raise _lib.CTError('all streams of a step must share the network input size')
+        if self._stager is None:
+            self._stager = FrameStager(self.device, B)
+        if self._launcher is None:
+            self._launcher = FrameLauncher(self.device, B)
+        cur = torch.cuda.current_stream()
+        staged = self._staged
+        if _raw_frame_source(frames, staged, slot) == RAW_STAGED:
+            self._staged = None
+            cur.wait_event(staged.event)
+        else:
+            self._forget_staged()
+            staged = self._stager.stage(frames, slot, False)
+        plane = 3 * H * W * 4
+        base = fr.data_ptr()
+        self._launcher.launch(frames, staged.bases, [m['trans_input'] for m in metas],
+                              [base + s * plane for s in range(B)],
+                              [base + (B + s) * plane if self.flip else None for s in range(B)], W, H,
+                              self._lut.data_ptr(), ctypes.c_void_p(cur.cuda_stream))
+        self._stager.read_by(staged, cur)
 
     # ---- one frame for every stream -------------------------------------------------------
     def _meta_transforms(self, m):
@@ -617,6 +682,12 @@ class StreamDetector(object):
             ctx.tin[s_] = np.asarray(metas[s_]['trans_input'], np.float64).reshape(-1)
         uploaded, self._prefetched = self._prefetched, None
         cur.slot, cur.frame, cur.next_frame = slot, None, None
+        if isinstance(images, (list, tuple)):      # VideoFrames: pre-processed into the slot by a launch on the loop stream
+            ctx.forget_upload(uploaded)
+            self._video_frames(ctx, slot, images, metas)
+            cur.frame_kind = _lib.CT_FRAME_IN_PLACE
+            return
+        self._forget_staged()
         cur.frame_kind = _frame_source(images, uploaded, slot)
         if cur.frame_kind != _lib.CT_FRAME_UPLOADED:
             ctx.forget_upload(uploaded)            # (a stale upload may still target this slot: drained BEFORE the copy)
@@ -643,6 +714,7 @@ class StreamDetector(object):
         t0 = time.time()
         n, loop = ctx.nslots, ctx.loop
         launched = ctx.launched
+        video = isinstance(images, (list, tuple))
         ahead = launched is not None and launched[0] is images and launched[1] == images._version
         if launched is not None and not ahead:
             self._drop_launched(ctx)
@@ -656,7 +728,8 @@ class StreamDetector(object):
         else:
             slot = ctx.slot
             self._native_stage_frame(ctx, cur, slot, images, metas)
-        can_prefetch = _prefetchable(prefetch, images.shape)
+        # (a float frame uploaded ahead is what ct_frame_loop_finish_submit launches: VideoFrames stage their bytes instead)
+        can_prefetch = not video and _prefetchable(prefetch, images.shape)
         t1 = time.time()
         if ahead:
             if can_prefetch:            # the frame after the one in flight: its slot was last read by the finished frame
@@ -671,6 +744,8 @@ class StreamDetector(object):
             ctx.slot = (slot + 1) % n
         if can_prefetch:
             self._prefetched = (prefetch, prefetch._version, (slot + 1) % n)
+        elif self._stageable(prefetch):
+            self._stage_video_ahead((slot + 1) % n, prefetch)
         # (the hook enqueues its reader of the device rows behind this frame's graph; the event it returns is waited
         # for ON THE STREAM right here, i.e. between this graph and the next one, whoever launches that)
         ev = self._gather(ctx)
@@ -698,18 +773,23 @@ class StreamDetector(object):
     def step(self, images, metas, timers=None, prefetch=None, prefetch_metas=None):
         """images: float32 [B,3,H,W] (already normalised, like PrefetchDataset hands over), or a list of B raw
         uint8 HxWx3 frames, which are uploaded as bytes and warped / normalised on the device
-        (``ct_preprocess_device``, bit-identical to ``Detector.pre_process``);
+        (``ct_preprocess_device``, bit-identical to ``Detector.pre_process``), or a list of B ``frames.VideoFrame``s -- BGR /
+        RGB / NV12 / I420, host or device memory, formats and sizes free per stream -- whose bytes are uploaded (or read in
+        place) and which ONE ``ct_preprocess_frames`` launch converts, warps and normalises for all streams (the same bits);
         metas: list of B ``meta`` dicts (image.make_meta).  Returns a list of B result lists.
         ``prefetch``: the float32 host tensor the NEXT call will pass as ``images`` (optional): its H2D copy is enqueued
         on a second HIP stream as soon as this frame's graph is launched and overlaps with it -- what the reference's
         ``DataLoader(pin_memory=True)`` + ``images.to(device, non_blocking=True)`` (test.py:74-76, detector.py:93-94) is
         for; the copy lands in the NEXT frame's own rotation slot, so the next call launches without any device copy.
+        A list of B ``VideoFrame``s as ``prefetch`` has their BYTES uploaded ahead the same way (``frames.FrameStager``); the
+        next call must pass the same objects, otherwise the staging is forgotten and the frames passed are uploaded then.
         ``prefetch_metas``: the metas the next call will pass (the same objects as ``metas`` for a video whose frames
         share one size): with them the native loop launches the next frame in the call that finishes this one."""
         opt = self.opt
         t0 = time.time()
         B = self.B
         raw_frames = isinstance(images, (list, tuple))
+        video = raw_frames and _is_video(images)
         if not raw_frames and self.flip and images.shape[0] == 2 * B:
             # what the reference's pre_process hands over under --flip_test (detector.py:225-226: the frame and its
             # mirrored copy): the mirrored half is rebuilt on the device by the frame's first launch
@@ -720,7 +800,8 @@ class StreamDetector(object):
         else:
             H, W = int(images.shape[2]), int(images.shape[3])
         ctx = self._context(H, W)
-        if (ctx.loop is not None and not raw_frames and all(self.started) and tuple(images.shape) == (B, 3, H, W)
+        if (ctx.loop is not None and all(self.started)
+                and (video if raw_frames else tuple(images.shape) == (B, 3, H, W))
                 and not getattr(opt, 'public_det', False) and not getattr(opt, 'zero_tracking', False)):
             return self._step_native(ctx, images, metas, timers, prefetch, prefetch_metas)
         self._drop_launched(ctx)
@@ -766,6 +847,10 @@ class StreamDetector(object):
             cur.wait_event(ctx.frame_ready)                    # uploaded by the previous step's ``prefetch``
         else:                     # (also THIS frame if the native loop's copy stream uploaded it: a wait on the host; rare path)
             ctx.forget_upload(uploaded)
+        if source is None and _is_video(images):
+            self._video_frames(ctx, slot, images, metas)
+            return
+        self._forget_staged()
         if source is None:
             for s in range(B):
                 self._warp_frame(s, images[s], metas[s], fr, H, W)
@@ -839,8 +924,16 @@ class StreamDetector(object):
             ctx.device_frame(slot)
         ctx.slot = (slot + 1) % ctx.nslots                     # this frame is the next step's pre_img (detector.py:148)
 
+    def _stageable(self, prefetch):
+        """may ``prefetch`` be staged ahead as bytes: a list of one VideoFrame per stream"""
+        return (isinstance(prefetch, (list, tuple)) and len(prefetch) == self.B
+                and all(isinstance(f, VideoFrame) for f in prefetch))
+
     def _prefetch_next(self, ctx, slot, prefetch):
         """the next frame's ``images.to(device, non_blocking=True)`` (test.py:74-76, detector.py:93-94), one step early"""
+        if self._stageable(prefetch):
+            self._stage_video_ahead((slot + 1) % ctx.nslots, prefetch)
+            return
         if not _prefetchable(prefetch, (self.B, 3) + ctx.hw):
             return
         # straight into the NEXT frame's slot: it was last read (as pre_img) by the previous frame's graph, which the
@@ -899,6 +992,7 @@ class StreamDetector(object):
         if self._ctx is not None:
             self._drop_launched(self._ctx)
             self._ctx.forget_upload(self._prefetched)
+        self._forget_staged()
         for s in (range(self.B) if stream is None else [stream]):
             self.trackers[s].reset()
             if self.fast is not None:
@@ -979,9 +1073,12 @@ class Detector(object):
         """the ``meta`` dict of detector.py:207-217,227-239 for a raw frame (c, s, trans_input, trans_output, calib,
         sizes; ``pre_dets`` / ``cur_dets`` carried over) -- everything pre_process returns except the pixels"""
         opt = self.opt
-        if image.dtype != np.uint8 or image.ndim != 3:
+        if isinstance(image, VideoFrame):
+            height, width = image.height, image.width
+        elif image.dtype != np.uint8 or image.ndim != 3:
             raise _lib.CTError('pre_process expects a uint8 HxWxC image (got %s %s)' % (image.dtype, image.shape))
-        height, width = image.shape[:2]
+        else:
+            height, width = image.shape[:2]
         meta = make_meta(getattr(opt, 'input_h', -1), getattr(opt, 'input_w', -1), height, width,
                          down_ratio=getattr(opt, 'down_ratio', 4), calib=input_meta.get('calib'),
                          focal_length=self.rest_focal_length, fix_res=bool(getattr(opt, 'fix_res', True)),
@@ -999,6 +1096,8 @@ class Detector(object):
             images, meta = self.parse_prefetched(x)
         elif torch.is_tensor(x):
             images = x
+        elif isinstance(x, VideoFrame):                        # a decoder's frame: bytes up, converted and warped on the device
+            images, meta = [x], self.frame_meta(x, meta)
         elif isinstance(x, (str, os.PathLike)) or isinstance(x, np.ndarray):
             if not isinstance(x, np.ndarray):                  # image file (detector.py:65-66; test.py:163)
                 x = imread_bgr(x)
@@ -1008,7 +1107,7 @@ class Detector(object):
             else:
                 images, meta = self.pre_process(x, 1.0, meta)
         else:
-            raise _lib.CTError('run() takes an image path, a uint8 image array, a normalised tensor + meta, or a '
+            raise _lib.CTError('run() takes an image path, a uint8 image array, a VideoFrame, a normalised tensor + meta, or a '
                                'pre-processed dict (got %s)' % type(x).__name__)
         loaded = time.time()
         timers = {}

@@ -882,6 +882,48 @@ int ct_preprocess_lut(const float *mean, const float *stdv, int channels, float 
 int ct_preprocess_device(const uint8_t *img, int h, int w, int stride, int channels, const double *trans,
                          int dst_w, int dst_h, const float *lut, float *out, float *out_flip, void *stream);
 
+/* ---- video frames as decoders deliver them (an addition under ABI 103) ------------------
+ * ct_preprocess_device for ALL frames of a step in ONE launch, from packed BGR / RGB or from YUV 4:2:0 surfaces.
+ * staging_host: n descriptors in pinned HOST memory; the call checks every argument on them, inverts each map in
+ * place like cv::warpAffine does, uploads them with ONE asynchronous copy (staging_host -> staging_dev, enqueued by
+ * the call itself) and launches once; frames of different sizes and formats share the launch, the output size
+ * dst_h x dst_w is common.  Per frame: out DEVICE fp32 [3, dst_h, dst_w], out_flip the mirrored copy or NULL.
+ * Planes are DEVICE u8 with a row pitch in bytes:
+ *   CT_PIX_BGR24   plane 0: [h, w, 3] packed B, G, R
+ *   CT_PIX_RGB24   the same with channels 0 and 2 exchanged on load
+ *   CT_PIX_NV12    plane 0: Y [h, w]; plane 1: U, V interleaved [h / 2, w]
+ *   CT_PIX_I420    plane 0: Y [h, w]; plane 1: U [h / 2, w / 2]; plane 2: V [h / 2, w / 2]
+ * Colour conversion (binding; the integer form OpenCV publishes for COLOR_YUV2BGR_NV12): chroma nearest, pixel
+ * (x, y) uses U, V at (x >> 1, y >> 1); Y' = max(0, Y - 16), u = U - 128, v = V - 128, coef = CY, CUB, CUG, CVG, CVR:
+ *   B = sat8((Y' CY + CUB u + 2^19) >> 20),  G = sat8((Y' CY + CUG u + CVG v + 2^19) >> 20),
+ *   R = sat8((Y' CY + CVR v + 2^19) >> 20)   (signed 32-bit, arithmetic shift)
+ * Each of the four taps is converted and saturated first and blended afterwards; a tap outside the frame is 0 in
+ * B, G, R.  The result equals ct_preprocess_device on the frame converted as a whole, bit for bit.
+ * CT_ERR_ARG before anything is enqueued: null pointers, n outside [1, CT_FRAMES_MAX], non-positive sizes, an
+ * unknown format, a null plane the format reads, a pitch below the row's bytes, odd h or w of a 4:2:0 frame, a
+ * matrix entry that is not finite. */
+#define CT_PIX_BGR24 0
+#define CT_PIX_RGB24 1
+#define CT_PIX_NV12 2
+#define CT_PIX_I420 3
+#define CT_FRAMES_MAX 1024
+typedef struct ct_frame_desc {
+    const uint8_t *plane[3];        /* DEVICE planes (unused ones ignored) */
+    int pitch[3];                   /* bytes per row of each plane */
+    int format, h, w;               /* CT_PIX_*; size of the frame in pixels */
+    int coef[5];                    /* CY, CUB, CUG, CVG, CVR (4:2:0 formats) */
+    int reserved;
+    double M[6];                    /* trans_input, the forward 2 x 3 map; the call writes the inverse over it */
+    float *out, *out_flip;
+} ct_frame_desc;
+typedef struct ct_frames_desc {
+    ct_frame_desc *staging_host;    /* pinned HOST [n] */
+    ct_frame_desc *staging_dev;     /* DEVICE [n] */
+    int n, dst_w, dst_h;
+    const float *lut;               /* DEVICE fp32 [3][256] (ct_preprocess_lut) */
+} ct_frames_desc;
+int ct_preprocess_frames(const ct_frames_desc *d, void *stream);
+
 /* ---- training targets on the device -------------------------------------------------
  * Replaces, for a whole batch, the dense part of the reference's GenericDataset.__getitem__
  * (src/lib/dataset/generic_dataset.py:205-255 _get_pre_dets, :330-370 _init_ret, :386-398 _mask_ignore_or_crowd,
