@@ -350,6 +350,13 @@ class OptimRec(ctypes.Structure):
                 ('reserved', ctypes.c_int * 13)]
 
 
+class OptimGuard(ctypes.Structure):
+    _fields_ = [('sumsq', ctypes.c_double), ('norm', ctypes.c_double), ('norm_sum', ctypes.c_double),
+                ('norm_max', ctypes.c_double), ('nonfinite', ctypes.c_longlong), ('steps', ctypes.c_longlong),
+                ('skipped', ctypes.c_longlong), ('clipped', ctypes.c_longlong), ('nonfinite_steps', ctypes.c_longlong),
+                ('coef', ctypes.c_float), ('skip', ctypes.c_int)]
+
+
 class SlotDesc(ctypes.Structure):
     _fields_ = [('map', ctypes.c_void_p), ('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
                 ('C', ctypes.c_int), ('ld', ctypes.c_int),
@@ -382,7 +389,8 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_finish_submit', 'ct_frame_loop_upload', 'ct_frame_loop_pending_slot', 'ct_frame_loop_in_flight',
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
            'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials',
-           'ct_optim_step', 'ct_slot_gather', 'ct_slot_fold']
+           'ct_optim_step', 'ct_slot_gather', 'ct_slot_fold',
+           'ct_optim_norms_workspace_bytes', 'ct_optim_norms', 'ct_optim_step_guarded']
 
 _lib = None
 
@@ -543,6 +551,10 @@ def load():
     lib.ct_build_inputs_partials.argtypes = [i, i]
     lib.ct_build_inputs.argtypes = [ctypes.POINTER(InputsDesc), p]
     lib.ct_optim_step.argtypes = [p, i, ctypes.c_longlong, i, p]
+    lib.ct_optim_norms_workspace_bytes.restype = sz
+    lib.ct_optim_norms_workspace_bytes.argtypes = [i, ctypes.c_longlong]
+    lib.ct_optim_norms.argtypes = [p, i, ctypes.c_longlong, ctypes.c_double, i, p, p, p, sz, p]
+    lib.ct_optim_step_guarded.argtypes = [p, i, ctypes.c_longlong, i, p, p]
     lib.ct_slot_gather.argtypes = [ctypes.POINTER(SlotDesc), p]
     lib.ct_slot_fold.argtypes = [ctypes.POINTER(SlotDesc), p]
     # CENTERTRACK_TUNE="key=value,key=value": launch-heuristic knobs of ct_set_tuning (A/B runs)

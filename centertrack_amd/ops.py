@@ -1159,3 +1159,25 @@ def optim_step(table, n, chunks, kind):
     """ct_optim_step (csrc/optim.hip) on the current stream: one launch over the ``n`` records and the chunk prefix of the
     DEVICE int32 tensor ``table`` (``centertrack_amd.optim.pack`` lays it out, the caller has uploaded it)."""
     _lib.check(_lib.load().ct_optim_step(table.data_ptr(), n, chunks, kind, _lib.stream_ptr()), 'ct_optim_step')
+
+
+def optim_norms_workspace_bytes(n, chunks):
+    """bytes of workspace ``optim_norms`` needs for ``n`` tensors in ``chunks`` chunks (0: sizes it refuses)"""
+    return int(_lib.load().ct_optim_norms_workspace_bytes(n, chunks))
+
+
+def optim_norms(table, n, chunks, max_norm, skip_nonfinite, per_tensor, guard, workspace):
+    """ct_optim_norms (csrc/optim.hip) on the current stream: two launches over the uploaded ``table``
+    that leave the sum of squares of every gradient in the DEVICE float64 tensor ``per_tensor`` (or ``None``) and norm, clip
+    coefficient, skip decision and running counters in the ``ct_optim_guard`` at the start of the DEVICE tensor
+    ``guard``.  ``workspace``: a DEVICE byte tensor of at least ``optim_norms_workspace_bytes(n, chunks)`` bytes."""
+    _lib.check(_lib.load().ct_optim_norms(table.data_ptr(), n, chunks, float(max_norm), int(bool(skip_nonfinite)),
+                                          per_tensor.data_ptr() if per_tensor is not None else None, guard.data_ptr(),
+                                          workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                          _lib.stream_ptr()), 'ct_optim_norms')
+
+
+def optim_step_guarded(table, n, chunks, kind, guard):
+    """ct_optim_step_guarded on the current stream: ``optim_step`` scaled by the guard's clip coefficient, or skipped"""
+    _lib.check(_lib.load().ct_optim_step_guarded(table.data_ptr(), n, chunks, kind, guard.data_ptr(), _lib.stream_ptr()),
+               'ct_optim_step_guarded')

@@ -17,6 +17,10 @@ No CPU fallback: parameters, gradients and state must be CUDA float32 contiguous
 ``maximize``, ``capturable``, ``differentiable``, ``decoupled_weight_decay``, ``nesterov``, ``dampening != 0`` and a
 tensor ``lr`` are refused with ``CTError``.  ``foreach`` / ``fused`` choose between torch's implementations and mean
 nothing here.
+
+The guarded step: ``optimizer.guard(max_norm=..., skip_nonfinite=...)`` puts ``ct_optim_norms`` in
+front of the update -- the global gradient norm, ``clip_grad_norm_``'s coefficient and a skip decision for gradients that
+are not finite, all of which stay on the device -- and ``grad_stats()`` reads them back on request.
 """
 import numpy as np
 import torch
@@ -117,7 +121,45 @@ def _fma(a, b, c, fused):
     return _FMA[dtype](a, b, c).astype(dtype)
 
 
-def reference_step(kind, p, g, state, hyper, fused=None):
+GUARD = np.dtype([('sumsq', '<f8'), ('norm', '<f8'), ('norm_sum', '<f8'), ('norm_max', '<f8'), ('nonfinite', '<i8'),
+                  ('steps', '<i8'), ('skipped', '<i8'), ('clipped', '<i8'), ('nonfinite_steps', '<i8'), ('coef', '<f4'),
+                  ('skip', '<i4')])                  # ct_optim_guard of include/centertrack_hip.h
+GUARD_SLOT = 128                                 # bytes the guard takes in front of the per-tensor sums of its buffer
+assert GUARD.itemsize <= GUARD_SLOT
+
+
+def norms_workspace_bytes(n, chunks):
+    """what ``ct_optim_norms_workspace_bytes`` answers, restated: 16 bytes per chunk and per tensor"""
+    if n < 1 or n > MAX_TENSORS or chunks < n or chunks >= 1 << 31:
+        return 0
+    return 16 * (chunks + n)
+
+
+def reference_guard(grads, max_norm=None, skip_nonfinite=False, dtype=np.float64, norm=None, eps=1e-6, clamp=True):
+    """The rule of ``ct_optim_norms`` on numpy arrays, for the tests: ``grads`` are the gradients of one step (``None``
+    entries are left out).  Returns ``sumsq`` (the squares added in float64, tensor by tensor), ``norm``, ``nonfinite``
+    (elements that are NaN or +-Inf), ``skip`` and ``coef``: 1 when ``max_norm`` is ``None`` or <= 0 or a gradient is
+    not finite, else ``c = max_norm / (norm + 1e-6)`` in double, clamped at 1 -- ``clip_grad_norm_``'s rule.  ``coef`` is
+    a ``dtype`` value: the device's float32, or the double torch's float64 tensors are scaled by.  ``norm``: a total norm
+    to use instead (torch's own, which adds in another order).  ``eps`` and ``clamp`` are the rule's two constants, there
+    so that a test can show what fails without them."""
+    grads = [np.asarray(g) for g in grads if g is not None]
+    per = [float((g.astype(np.float64).ravel() ** 2).sum()) for g in grads]
+    sumsq = 0.0
+    for x in per:
+        sumsq += x
+    nonfinite = int(sum(int((~np.isfinite(g)).sum()) for g in grads))
+    norm = float(np.sqrt(sumsq)) if norm is None else float(norm)
+    coef = 1.0
+    if max_norm is not None and max_norm > 0 and nonfinite == 0:
+        with np.errstate(divide='ignore'):
+            c = float(np.float64(max_norm) / np.float64(norm + eps))
+        coef = c if (c < 1.0 or not clamp) else 1.0
+    return dict(sumsq=sumsq, norm=norm, per_tensor=per, nonfinite=nonfinite, skip=bool(nonfinite > 0 and skip_nonfinite),
+                coef=np.dtype(dtype).type(coef))
+
+
+def reference_step(kind, p, g, state, hyper, fused=None, guard=None, zero_first=True):
     """One step of torch's single-tensor Adam / SGD (``foreach=False``) on numpy arrays, in ``p``'s dtype (float64 or
     float32), as torch's CPU kernels compute it: the scalars are formed in double and rounded to that dtype; the
     operations come in the kernels' order.  ``p`` and ``state`` (``{}`` before the first step; ``step`` an int) are
@@ -129,11 +171,29 @@ def reference_step(kind, p, g, state, hyper, fused=None):
     once there (a fused multiply-add).  And the square root is torch's own: its vectorised CPU square root is not
     correctly rounded (it differs from numpy's in 0.7% of float64 values), so no restatement reproduces it.
     The device kernel (csrc/optim.hip) fuses nothing, rounds division and square root correctly and forms
-    ``-step_size (m / denom)`` where the CPU kernel forms ``(-step_size m) / denom``."""
+    ``-step_size (m / denom)`` where the CPU kernel forms ``(-step_size m) / denom``.
+
+    ``guard``: what ``reference_guard`` returned for this step's gradients.  ``g * coef`` (one product in ``p``'s dtype)
+    takes the place of ``g``; under ``skip`` nothing moves, but Adam's ``step`` still advances (the host cannot know of
+    the skip) and an SGD momentum buffer this step was to create is created as zeros (``zero_first``; the next step's
+    ``momentum * 0 + g`` is then torch's first step)."""
     if fused is None:
         fused = torch.backends.cpu.get_cpu_capability() != 'DEFAULT'
     dt = p.dtype.type
     g = np.asarray(g, p.dtype)
+    if guard is not None:
+        if guard['skip']:
+            if kind == 'adam':
+                if not state:
+                    state.update(step=0, exp_avg=np.zeros_like(p), exp_avg_sq=np.zeros_like(p))
+                state['step'] += 1
+            elif kind == 'sgd':
+                if hyper.get('momentum', 0) != 0 and 'momentum_buffer' not in state and zero_first:
+                    state['momentum_buffer'] = np.zeros_like(p)
+            else:
+                raise CTError('optim.reference_step: kind %r is neither "adam" nor "sgd"' % (kind,))
+            return
+        g = g * dt(guard['coef'])
     wd = hyper.get('weight_decay', 0)
     if kind == 'adam':
         if not state:
@@ -208,8 +268,109 @@ class _FusedStep(object):
             for c in visited:
                 c[6] = c[5]._version
 
+    def guard(self, max_norm=None, skip_nonfinite=False):
+        """Put the device-side guard in front of every later ``step()``; returns ``self``.
+
+        ``max_norm`` > 0: the gradients are scaled by ``torch.nn.utils.clip_grad_norm_``'s coefficient ``min(1, max_norm /
+        (norm + 1e-6))`` over all tensors of the optimizer that have a gradient (2-norm; the coefficient is formed in
+        double and applied as one float32 product inside the update).  ``skip_nonfinite``: a step whose gradients hold a
+        NaN or an Inf changes no parameter and no state.  ``guard()`` with both off restores the unguarded ``step()``.
+
+        A guarded ``step()`` enqueues one copy and three launches and still waits for nothing; its buffers are allocated
+        once and grown on demand.  What differs from torch: ``p.grad`` is NOT scaled in place (``clip_grad_norm_``
+        does that), and the host counts every ``step()`` call, also one the device skips -- it cannot know of the skip
+        without waiting -- so ``state['step']`` and ``state_dict`` advance as torch's do and the bias correction after
+        a skipped step is one step ahead.  (``GradScaler`` differs there: it does not call ``step``.)  All parameters
+        must be on one device.  ``grad_stats()`` reads the outcome."""
+        max_norm = 0.0 if max_norm is None else float(max_norm)
+        if max_norm != max_norm:
+            raise CTError('centertrack_amd.optim.%s.guard: max_norm is NaN' % type(self).__name__)
+        on = max_norm > 0 or bool(skip_nonfinite)
+        self.__dict__['_guard'] = (max_norm if max_norm > 0 else 0.0, bool(skip_nonfinite)) if on else None
+        return self
+
+    def _guard_buffers(self, device, n, chunks, words):
+        """the table, the guard with the per-tensor sums behind it and the workspace of a guarded step: kept, grown by
+        doubling (the guard's counters move along)"""
+        b = self.__dict__.setdefault('_gbufs', {'device': device, 'table': None, 'state': None, 'work': None, 'cap': 0,
+                                                'n': 0, 'last': None})
+        if b['device'] != device:
+            raise CTError('centertrack_amd.optim.%s: a guarded step takes the parameters of one device (got %s and %s)'
+                          % (type(self).__name__, b['device'], device))
+
+        def grown(have, need):
+            cap = max(have, 1024)
+            while cap < need:
+                cap *= 2
+            return cap
+        if b['table'] is None or b['table'].numel() < words:
+            b['table'] = torch.empty(grown(0 if b['table'] is None else b['table'].numel(), words), dtype=torch.int32,
+                                     device=device)
+        if b['state'] is None or b['cap'] < n:
+            cap = grown(b['cap'], n)
+            state = torch.zeros(GUARD_SLOT + 8 * cap, dtype=torch.uint8, device=device)
+            if b['state'] is not None:
+                state[:GUARD_SLOT].copy_(b['state'][:GUARD_SLOT])
+            b['state'], b['cap'] = state, cap
+        need = norms_workspace_bytes(n, chunks)
+        if b['work'] is None or b['work'].numel() < need:
+            b['work'] = torch.empty(grown(0 if b['work'] is None else b['work'].numel(), need), dtype=torch.uint8,
+                                    device=device)
+        b['n'] = n
+        return b
+
+    def _launch_guarded(self, per_device, guard):
+        from . import ops
+        if len(per_device) > 1:
+            raise CTError('centertrack_amd.optim.%s: a guarded step takes the parameters of one device (got %s)'
+                          % (type(self).__name__, sorted(str(d) for d in per_device)))
+        ring = self.__dict__.setdefault('_ring', [])
+        for device, items in per_device.items():
+            words = table_words(len(items))
+            entry = _staging.take(ring, words, torch.int32)
+            _, n, chunks = pack(self._kind, items, out=entry['host'].numpy())
+            with torch.cuda.device(device):
+                b = self._guard_buffers(device, n, chunks, words)
+                stream = torch.cuda.current_stream()
+                if b['last'] is not None and b['last'][0] != stream.cuda_stream:
+                    stream.wait_event(b['last'][1])          # (the buffers are shared between steps: keep them in order)
+                b['table'][:words].copy_(entry['host'][:words], non_blocking=True)
+                ops.optim_norms(b['table'], n, chunks, guard[0], guard[1], b['state'][GUARD_SLOT:], b['state'], b['work'])
+                ops.optim_step_guarded(b['table'], n, chunks, self._kind, b['state'])
+                entry['event'].record()
+                b['last'] = (stream.cuda_stream, entry['event'])
+
+    def guard_counters(self):
+        """the guard's running ``[norm_sum, steps, skipped, clipped, nonfinite_steps]`` as a float64 DEVICE tensor (no
+        wait), or ``None`` before the first guarded step"""
+        b = self.__dict__.get('_gbufs')
+        if self.__dict__.get('_guard') is None or b is None or b['state'] is None:
+            return None
+        st = b['state']
+        return torch.cat([st[16:24].view(torch.float64), st[40:72].view(torch.int64).double()])
+
+    def grad_stats(self):
+        """What the last guarded ``step()`` found, read from the device (the one call of the guard that waits): ``norm``,
+        ``sumsq``, ``nonfinite``, ``coef``, ``skip`` of that step; the running ``steps``, ``skipped``, ``clipped``,
+        ``nonfinite_steps``, ``norm_max`` and ``norm_mean`` (over the steps whose gradients were finite); ``per_tensor``,
+        the norm of every tensor that had a gradient in that step, in the optimizer's order."""
+        b = self.__dict__.get('_gbufs')
+        if b is None or b['state'] is None:
+            raise CTError('centertrack_amd.optim.%s.grad_stats: no guarded step has run' % type(self).__name__)
+        host = b['state'][:GUARD_SLOT + 8 * b['n']].cpu().numpy()
+        g = host[:GUARD.itemsize].view(GUARD)[0]
+        out = {k: (float(g[k]) if GUARD[k].kind == 'f' else int(g[k])) for k in GUARD.names if k != 'norm_sum'}
+        out['skip'] = bool(out['skip'])
+        finite = out['steps'] - out['nonfinite_steps']
+        out['norm_mean'] = float(g['norm_sum']) / finite if finite else 0.0
+        out['per_tensor'] = np.sqrt(host[GUARD_SLOT:].view(np.float64))
+        return out
+
     def _launch(self, per_device):
         from . import ops
+        guard = self.__dict__.get('_guard')
+        if guard is not None:
+            return self._launch_guarded(per_device, guard)
         ring = self.__dict__.setdefault('_ring', [])
         for device, items in per_device.items():
             words = table_words(len(items))
@@ -364,8 +525,51 @@ class SGD(_FusedStep, torch.optim.SGD):
         return loss
 
 
+_NORM_RING = []
+
+
+def grad_norms(params):
+    """The 2-norm of the gradients of ``params`` (parameters with a ``.grad``, or the gradient tensors themselves) by
+    ``ct_optim_norms``, without an optimizer: ``(total, per_tensor)``, a float64 scalar and a float64 vector on the
+    device, in the order given; parameters without a gradient are left out.  No host wait."""
+    from . import ops
+    grads = []
+    for t in params:
+        g = t.grad if getattr(t, 'grad', None) is not None or getattr(t, 'requires_grad', False) else t
+        if g is None or g.numel() == 0:
+            continue
+        _check_tensor(g, None, 'a gradient', 'centertrack_amd.optim.grad_norms')
+        if grads and g.device != grads[0].device:
+            raise CTError('centertrack_amd.optim.grad_norms: gradients on %s and %s' % (grads[0].device, g.device))
+        grads.append(g.detach())
+    if not grads:
+        raise CTError('centertrack_amd.optim.grad_norms: no gradient')
+    device = grads[0].device
+    items = [(g.data_ptr(), g.data_ptr(), 0, 0, g.numel(), (0.0, 0.0, 0.0), 0) for g in grads]   # (p is never read)
+    words = table_words(len(items))
+    entry = _staging.take(_NORM_RING, words, torch.int32)
+    _, n, chunks = pack(_lib.CT_OPTIM_SGD, items, out=entry['host'].numpy())
+    with torch.cuda.device(device):
+        table = torch.empty(words, dtype=torch.int32, device=device)
+        table.copy_(entry['host'][:words], non_blocking=True)
+        state = torch.zeros(GUARD_SLOT + 8 * n, dtype=torch.uint8, device=device)
+        work = torch.empty(norms_workspace_bytes(n, chunks), dtype=torch.uint8, device=device)
+        ops.optim_norms(table, n, chunks, 0.0, False, state[GUARD_SLOT:], state, work)
+        entry['event'].record()
+    return state[8:16].view(torch.float64)[0], state[GUARD_SLOT:].view(torch.float64).sqrt()
+
+
+def guard_options(opt):
+    """``(max_norm or None, skip_nonfinite)`` from ``opt.max_grad_norm`` / ``opt.skip_nonfinite``, both optional"""
+    max_norm = getattr(opt, 'max_grad_norm', None)
+    if max_norm is not None and not max_norm > 0:
+        max_norm = None
+    return max_norm, bool(getattr(opt, 'skip_nonfinite', False))
+
+
 def get_optimizer(opt, model):
-    """the reference's src/main.py:17-26 with the classes above"""
+    """the reference's src/main.py:17-26 with the classes above; ``opt.max_grad_norm`` / ``opt.skip_nonfinite``, where an
+    ``opt`` has them, switch the guard on"""
     if opt.optim == 'adam':
         optimizer = Adam(model.parameters(), opt.lr)
     elif opt.optim == 'sgd':
@@ -373,4 +577,7 @@ def get_optimizer(opt, model):
         optimizer = SGD(model.parameters(), opt.lr, momentum=0.9, weight_decay=0.0001)
     else:
         assert 0, opt.optim
+    max_norm, skip_nonfinite = guard_options(opt)
+    if max_norm is not None or skip_nonfinite:
+        optimizer.guard(max_norm, skip_nonfinite)
     return optimizer

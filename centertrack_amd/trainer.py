@@ -10,6 +10,11 @@ the averages are the ``AverageMeter``'s to the bit -- and the host reads them ev
 package (``dla_seg.DLASeg``, ``heads.HeadFinetuner``), the loss is ``losses.GenericLoss``, the optimizer either
 ``centertrack_amd.optim``'s or torch's.
 
+``opt.max_grad_norm`` / ``opt.skip_nonfinite`` (both optional attributes) switch on the optimizer's device-side guard
+(``optim.Adam.guard``).  With a guard on, the ``print_iter`` line carries the epoch's mean gradient
+norm, the closing line the number of skipped steps as well, and ``ret`` gains ``'grad_norm'`` and ``'skipped'``; they
+come in the same device read as the loss sums, so the loop waits no more often.  With the guard off nothing changes.
+
 Not covered: more than one GPU (``DataParallel``), ``opt.debug > 0`` (the reference's drawing), the progress bar (a plain
 line is printed instead).
 """
@@ -20,6 +25,7 @@ import torch
 from . import dcn_v2
 from ._lib import CTError
 from .losses import GenericLoss
+from .optim import guard_options
 
 LOSS_ORDER = ('hm', 'wh', 'reg', 'ltrb', 'hps', 'hm_hp', 'hp_offset', 'dep', 'dim', 'rot', 'amodel_offset', 'ltrb_amodal',
               'tracking', 'nuscenes_att', 'velocity')
@@ -49,6 +55,12 @@ class Trainer(object):
         self._refuse_debug(opt)
         self.opt = opt
         self.optimizer = optimizer
+        max_norm, skip_nonfinite = guard_options(opt)
+        if optimizer is not None and (max_norm is not None or skip_nonfinite):
+            if not hasattr(optimizer, 'guard'):
+                raise CTError('centertrack_amd.trainer.Trainer: opt.max_grad_norm / opt.skip_nonfinite need an optimizer of '
+                              'centertrack_amd.optim (got %s)' % type(optimizer).__name__)
+            optimizer.guard(max_norm, skip_nonfinite)
         self.loss_stats, self.loss = self._get_losses(opt)
         self.model_with_loss = ModelWithLoss(model, self.loss)
         self.device = getattr(opt, 'device', None)
@@ -95,12 +107,30 @@ class Trainer(object):
         title = '{}/{}'.format(getattr(opt, 'task', ''), getattr(opt, 'exp_id', ''))
         sums, count, done = None, 0, 0
         start = time.time()
+        # the optimizer's guard, when it is on: its running counters at the start of the epoch, on the device
+        counters = getattr(self.optimizer, 'guard_counters', None) if train else None
+        guarded = counters is not None and getattr(self.optimizer, '_guard', None) is not None
+        base = counters() if guarded else None
 
-        def line(host_sums):
+        def line(host_sums, guard=None, closing=False):
             text = '{}| {}: [{}][{}/{}]|Tot: {:.1f}s '.format(title, phase, epoch, done, num_iters, time.time() - start)
             for l, s in zip(names, host_sums):
                 text += '|{} {:.4f} '.format(l, s / count if count else 0.0)
+            if guard is not None:
+                text += '|grad_norm {:.4f} '.format(guard[0])
+                if closing:
+                    text += '|skipped {} '.format(guard[1])
             return text
+
+        def read_guarded():
+            """the loss sums and the guard's counters of this epoch in ONE device read: (sums, (mean norm, skipped))"""
+            cur = counters()
+            if cur is None or sums is None:
+                return (sums.cpu().tolist() if sums is not None else [0.0] * len(names)), (0.0, 0)
+            host = torch.cat([sums, cur if base is None else cur - base]).cpu().tolist()
+            norm_sum, steps, skipped, _, nonfinite_steps = host[len(names):]
+            finite = steps - nonfinite_steps
+            return host[:len(names)], (norm_sum / finite if finite else 0.0, int(skipped))
 
         with dcn_v2.trainable(train or dcn_v2.is_trainable()):
             for iter_id, batch in enumerate(data_loader):
@@ -122,12 +152,21 @@ class Trainer(object):
                 count += n
                 done = iter_id + 1
                 if print_iter > 0 and iter_id % print_iter == 0:
-                    print(line(sums.cpu().tolist()))                      # the only per-iteration read, on request
+                    if guarded:
+                        print(line(*read_guarded()))
+                    else:
+                        print(line(sums.cpu().tolist()))                  # the only per-iteration read, on request
                 del output, loss, loss_stats
-        host_sums = sums.cpu().tolist() if sums is not None else [0.0] * len(names)   # waits for the epoch's last launch
+        guard = None
+        if guarded:
+            host_sums, guard = read_guarded()
+        else:
+            host_sums = sums.cpu().tolist() if sums is not None else [0.0] * len(names)   # waits for the epoch's last launch
         ret = {l: (s / count if count else 0) for l, s in zip(names, host_sums)}
+        if guarded:
+            ret['grad_norm'], ret['skipped'] = guard
         ret['time'] = (time.time() - start) / 60.
-        print(line(host_sums))
+        print(line(host_sums, guard, closing=True))
         return ret, results
 
     def val(self, epoch, data_loader):

@@ -1065,6 +1065,54 @@ typedef struct ct_optim_rec {
 } ct_optim_rec;
 int ct_optim_step(const void *table, int n, long long chunks, int kind, void *stream);
 
+/* ---- guarded optimizer step (an addition under ABI 103) -----------------------------------
+ * The global gradient norm, torch.nn.utils.clip_grad_norm_'s clip coefficient and a "skip the step when a gradient is
+ * not finite" decision, all formed and consumed on the device: no host read between the norm and the update.
+ *
+ * ct_optim_norms makes two launches over the table ct_optim_step reads (only g and numel of a record are used; p, m, v
+ * are never read).
+ *   Pass 1 walks the chunks as ct_optim_step does (grid min(chunks, 2048), strided, binary search in the prefix).  For
+ *   chunk c it forms the sum of (double)g[i] * (double)g[i] -- every product is exact in double -- and counts the
+ *   elements that are NaN or +-Inf, with 16-byte loads when the record's g is 16-byte aligned, element by element
+ *   otherwise and for the last numel % 4 elements.  The order of the additions is fixed and does not depend on the
+ *   alignment: lane l of 256 adds elements 4 (l + 256 k) + e in the order k = 0..3, e = 0..3; the 64 lanes of a wave
+ *   are added in a butterfly (xor 32, 16, .. 1), the four waves in the order ((w0 + w1) + w2) + w3 through LDS.  One
+ *   16-byte record per chunk (the double, the int count, a zero word) is stored at workspace[c].
+ *   Pass 2 is one launch of one workgroup, whatever the data: the chunk partials of tensor t are added in chunk order
+ *   into per-tensor sums (stored behind the chunk records in the workspace, and in per_tensor[t] when per_tensor is
+ *   not NULL: n doubles, the SUM OF SQUARES of tensor t), the per-tensor sums in tensor order into S, the counts into
+ *   F.  All in double, no atomics.  The chunking comes from the prefix alone and the orders are fixed, so S has the
+ *   same bits from run to run and whatever the grid of pass 1.
+ * Pass 2 then writes *guard (DEVICE memory; the caller allocates it once and zeroes it once):
+ *   sumsq = S, norm = sqrt(S), nonfinite = F, skip = (F > 0 && skip_nonfinite),
+ *   coef = 1.0f when max_norm <= 0 or F > 0; otherwise c = max_norm / (norm + 1e-6) in double and
+ *          coef = c < 1 ? (float)c : 1.0f   (clip_grad_norm_'s rule),
+ *   and the running counters only this launch updates: steps += 1; nonfinite_steps += (F > 0); skipped += skip;
+ *   clipped += (coef < 1 && !skip); on steps with F == 0, norm_sum += norm and norm_max = max(norm_max, norm).
+ *
+ * ct_optim_step_guarded is ct_optim_step reading guard->skip and guard->coef (uniform loads) first.  skip != 0: no byte
+ * of p, m, v is written -- except that the momentum buffer of an SGD record with first != 0 is filled with zeros, so
+ * that the NEXT step's m = momentum m + g gives the m = g of torch's first step.  Otherwise g' = g * coef (one float32
+ * product, no contraction) takes the place of g and the arithmetic of ct_optim_step follows unchanged; coef = 1.0f
+ * gives ct_optim_step's bits.  The gradient tensors are NEVER written: clip_grad_norm_ scales .grad in place, this
+ * does not, so p.grad after the step still holds the unclipped gradient.
+ *
+ * CT_ERR_ARG before anything is enqueued: what ct_optim_step refuses (ct_optim_norms takes no kind), a null guard, a
+ * null workspace, workspace_bytes below ct_optim_norms_workspace_bytes(n, chunks), a max_norm that is NaN.
+ * ct_optim_norms_workspace_bytes is 16 (chunks + n), and 0 for an n or chunks the calls refuse. */
+typedef struct ct_optim_guard {
+    double sumsq, norm;             /* of the last ct_optim_norms */
+    double norm_sum, norm_max;      /* running, over the steps with nonfinite == 0 */
+    long long nonfinite;            /* of the last ct_optim_norms: elements that are NaN or +-Inf */
+    long long steps, skipped, clipped, nonfinite_steps;     /* running */
+    float coef;                     /* what ct_optim_step_guarded multiplies every gradient element by */
+    int skip;                       /* != 0: ct_optim_step_guarded leaves p, m, v alone */
+} ct_optim_guard;
+size_t ct_optim_norms_workspace_bytes(int n, long long chunks);
+int ct_optim_norms(const void *table, int n, long long chunks, double max_norm, int skip_nonfinite, double *per_tensor,
+                   ct_optim_guard *guard, void *workspace, size_t workspace_bytes, void *stream);
+int ct_optim_step_guarded(const void *table, int n, long long chunks, int kind, const ct_optim_guard *guard, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
