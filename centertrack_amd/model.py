@@ -23,8 +23,6 @@ from .weights import CHANNELS, LEVELS, dla34_param_shapes
 BN_EPS = 1e-5
 FUSE_OFFSET = os.environ.get('CENTERTRACK_FUSE_OFFSET', '1') != '0'
 WINOGRAD = os.environ.get('CENTERTRACK_WINOGRAD', '1') != '0'
-FUSE_HEADS = os.environ.get('CENTERTRACK_FUSE_HEADS', '1') != '0'
-FOLD_POOL = os.environ.get('CENTERTRACK_FOLD_POOL', '1') != '0'       # 2x2 max-pools as side outputs of the stride-2 convs
 FUSE_PROJ = os.environ.get('CENTERTRACK_FUSE_PROJ', '1') != '0'       # Tree.project computed by the tree1.conv1 launch (round 4)
 
 
@@ -35,13 +33,60 @@ def _fold_bn(sd, p):
     return scale.float().contiguous(), shift.float().contiguous()
 
 
-class _Launch(object):
-    """One pre-built C-ABI call of the frame (`keep` pins the tensors its raw pointers refer to)."""
-    __slots__ = ('fn', 'args', 'name', 'keep', 'us', 'ws_need')
+def _wino(w):
+    """Winograd F(2x2,3x3) form of a 3x3 weight the stride-1 layers may be run with (autotuner's choice)"""
+    ok = WINOGRAD and w.shape[2] == 3 and w.shape[1] % 64 == 0
+    return ops.pack_winograd(w) if ok else None
 
-    def __init__(self, name, fn, args, keep=(), reads=(), writes=(), us=5.0, ws_need=0):
+
+class _Launch(object):
+    """One pre-built C-ABI call of the frame (`keep` pins the tensors its raw pointers refer to; `out`: the view or NCHW
+    tensor it writes, None for a group launch)."""
+    __slots__ = ('fn', 'args', 'name', 'keep', 'out', 'ws_need')
+
+    def __init__(self, name, fn, args, keep=(), out=None, ws_need=0):
         self.name, self.fn, self.args, self.keep = name, fn, args, keep
-        self.us, self.ws_need = us, ws_need
+        self.out, self.ws_need = out, ws_need
+
+
+def _conv_launch(name, d, keep, out, dev, tune):
+    """The _Launch of one ct_conv2d call: ``d`` is the filled ConvDesc, the autotuner (``tune``) picks its launch shape
+    and the library says how much split-K workspace that shape wants (_share_conv_workspace hands it out)."""
+    if tune:
+        autotune.tune_conv(d, dev)
+    return _Launch(name, 'conv', d, keep, out=out, ws_need=_lib.load().ct_conv2d_workspace_bytes(ctypes.byref(d)))
+
+
+def _share_conv_workspace(launches, dev):
+    """split-K partials of the dense convs: one workspace shared by all of them (the launches of a frame are
+    sequential); every DCN layer owns its workspace (the layers of a group run concurrently)"""
+    need = max([l.ws_need for l in launches if l.fn == 'conv'] + [16])
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    for l in launches:
+        if l.fn == 'conv':
+            l.args.workspace, l.args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    return ws
+
+
+class _Builder(object):
+    """What the stages of one plan build share: the launch list, the batch, the device, whether the autotuner runs."""
+
+    def __init__(self, N, dev, tune):
+        self.N, self.dev, self.tune, self.launches = N, dev, tune, []
+
+    def alloc(self, h, w, c):
+        return ops.new_view(self.N, h, w, c, self.dev)
+
+    def conv(self, name, d, keep, out):
+        self.launches.append(_conv_launch(name, d, keep, out, self.dev, self.tune))
+        return out
+
+    def conv_bn(self, name, x, pk, cout, ks, stride=1, relu=True, res=None, out=None, **kw):
+        """conv + folded BN (+ residual, ReLU) of the trunk; ``pk`` = (packed weight, scale, shift, Winograd form)"""
+        wp, sc, sh, ww = pk
+        d = ops.make_conv_desc(x, wp, cout, ks, stride, scale=sc, shift=sh, res=res, relu=relu, out=out,
+                               w_wino=(ww if stride == 1 else None), **kw)
+        return self.conv(name, d, (x, res, out, pk, kw.get('pool'), kw.get('proj')), out)
 
 
 # The views of one DeformConv node of the IDAUp tree (dla.py:506-518): input view, output view, the fused IDAUp step
@@ -111,14 +156,9 @@ class DLASegHIP(torch.nn.Module):
         sd = {k: v.to(dev) for k, v in self.state_dict().items()}
         P = {}
 
-        def wino(w):
-            """Winograd F(2x2,3x3) form of a 3x3 weight the stride-1 layers may be run with (autotuner's choice)"""
-            ok = WINOGRAD and w.shape[2] == 3 and w.shape[1] % 64 == 0
-            return ops.pack_winograd(w) if ok else None
-
         def conv_bn(wkey, bnkey):
             sc, sh = _fold_bn(sd, bnkey)
-            return ops.pack_weight(sd[wkey]), sc, sh, wino(sd[wkey])
+            return ops.pack_weight(sd[wkey]), sc, sh, _wino(sd[wkey])
 
         P['stem_w'] = [sd['base.base_layer.0.weight'].contiguous(),
                        sd['base.pre_img_layer.0.weight'].contiguous() if self.pre_img else None,
@@ -156,7 +196,7 @@ class DLASegHIP(torch.nn.Module):
             sh = (sd[p + '.conv.bias'].double() * sc.double() + sh.double()).float().contiguous()
             return {'w': ops.pack_weight(sd[p + '.conv.weight']), 'scale': sc, 'shift': sh,
                     'w_off': ops.pack_weight(sd[p + '.conv.conv_offset_mask.weight']),
-                    'w_off_wino': wino(sd[p + '.conv.conv_offset_mask.weight']),
+                    'w_off_wino': _wino(sd[p + '.conv.conv_offset_mask.weight']),
                     'b_off': sd[p + '.conv.conv_offset_mask.bias'].contiguous()}
 
         for p, n in (('dla_up.ida_0', 1), ('dla_up.ida_1', 2), ('dla_up.ida_2', 3), ('ida_up', 2)):
@@ -164,181 +204,181 @@ class DLASegHIP(torch.nn.Module):
                 P['%s.proj_%d' % (p, k)] = deform('%s.proj_%d' % (p, k))
                 P['%s.node_%d' % (p, k)] = deform('%s.node_%d' % (p, k))
                 P['%s.up_%d' % (p, k)] = ops.upsample_weight(sd['%s.up_%d.weight' % (p, k)])
-        # heads with <= 8 output channels: ONE launch for conv3x3 + ReLU + conv1x1 of all of them (ct_heads_fused)
-        hc = self.head_conv
-        # ('hm_hp' stays out whatever its width: ct_heads_fused has ONE sigmoid range, taken by 'hm'; the per-head 1x1
-        # tail applies hm_hp's sigmoid, detector.py:300-304)
-        small = ([h for h, c in self.heads.items() if c <= 8 and h != 'hm_hp']
-                 if (FUSE_HEADS and WINOGRAD and hc == 256) else [])
-        small = small[:_lib.CT_MAX_FUSED_HEADS]
-        P['heads_small'] = small
-        def fused(names):
-            """(w0 Winograd-packed, b0, w2 [n,8,256], b2 [n,8]) of ct_heads_fused for the heads ``names``"""
-            w0s = torch.cat([sd[h + '.0.weight'] for h in names], 0)
-            w2s = torch.zeros((len(names), 8, hc), device=dev)
-            b2s = torch.zeros((len(names), 8), device=dev)
-            for i, h in enumerate(names):
-                c = self.heads[h]
-                w2s[i, :c] = sd[h + '.2.weight'].reshape(c, hc)
-                b2s[i, :c] = sd[h + '.2.bias']
-            return (ops.pack_winograd(w0s), torch.cat([sd[h + '.0.bias'] for h in names], 0).contiguous(),
-                    w2s.contiguous(), b2s.contiguous())
-
-        if small:
-            P['hs:' + ','.join(small)] = fused(small)
-            if 'hm' in small and small != ['hm']:
-                P['hs:hm'] = fused(['hm'])             # (sparse-heads plans: the dense launch holds 'hm' alone)
-        big = [h for h in self.heads if h not in small]
-        P['heads_big'] = big
-        if small and big:                  # the remaining (wide) heads keep the two-launch form on their own channels
-            w0b = torch.cat([sd[h + '.0.weight'] for h in big], 0)
-            P['hb_w'], P['hb_ww'] = ops.pack_weight(w0b), wino(w0b)
-            P['hb_b'] = torch.cat([sd[h + '.0.bias'] for h in big], 0).contiguous()
-            if 'hm_hp' in big and big != ['hm_hp']:          # (sparse-pose plans: hm_hp is the only wide head left)
-                w0b = sd['hm_hp.0.weight']
-                P['hb_w:hm_hp'], P['hb_ww:hm_hp'] = ops.pack_weight(w0b), wino(w0b)
-                P['hb_b:hm_hp'] = sd['hm_hp.0.bias'].contiguous()
-        # heads: all first layers share their input -> one 64 -> 256*nh conv
-        w0 = torch.cat([sd[h + '.0.weight'] for h in self.heads], 0)
-        P['head0_w'] = ops.pack_weight(w0)
-        P['head0_ww'] = wino(w0)
-        P['head0_b'] = torch.cat([sd[h + '.0.bias'] for h in self.heads], 0).contiguous()
-        # ... and all second (1x1) layers as ONE block-diagonal 256*nh -> sum(c) conv: a single launch reads
-        # the intermediate once and writes every head into channel slices of one NCHW tensor
-        hc = self.head_conv
-        ctot = sum(self.heads.values())
-        w2 = torch.zeros((ctot, hc * len(self.heads), 1, 1), device=dev)
-        c0 = 0
-        for j, (h, c) in enumerate(self.heads.items()):
-            w2[c0:c0 + c, hc * j:hc * (j + 1)] = sd[h + '.2.weight']
-            c0 += c
-        P['head2_w'] = ops.pack_weight(w2)
-        P['head2_b'] = torch.cat([sd[h + '.2.bias'] for h in self.heads], 0).contiguous()
-        for h in self.heads:      # per-head form, used when the block-diagonal one would waste too many flops
-            P[h + '.2'] = (ops.pack_weight(sd[h + '.2.weight']), sd[h + '.2.bias'].contiguous())
-        # sparse heads (round 5, opt-in): the regression heads the decode only reads at the K winners -- direct-form
-        # packed conv3x3 weights (the Winograd form has no single-pixel evaluation), hidden bias, [c, 256] output layer
-        if hc == 256:
-            for h, c in self.heads.items():
-                if h in _lib.HEAD_INDEX or h in ('hps', 'hp_offset'):
-                    P['sparse.' + h] = (ops.pack_weight(sd[h + '.0.weight']), sd[h + '.0.bias'].contiguous(),
-                                        sd[h + '.2.weight'].reshape(c, hc).contiguous(), sd[h + '.2.bias'].contiguous())
         self._prepared = P
         return P
 
-    def _winner_heads(self, P, feat):
+    # --- head weights: packed the first time a plan asks for them -----------------------------------------
+    def _packed(self, kind, names):
+        """``_pack_<kind>`` of the heads ``names``, cached in the prepared dict under (kind, names): a trunk-only plan
+        (heads.HeadFinetuner) packs no head weights, and load_state_dict / HeadFinetuner.commit() drop the packings
+        with the dict."""
+        P = self._prepare()
+        key = (kind, tuple(names))
+        if key not in P:
+            P[key] = getattr(self, '_pack_' + kind)(self.state_dict(), list(names))
+        return P[key]
+
+    def _pack_first(self, sd, names):
+        """(packed weight, Winograd form, bias) of the first layers of ``names``: they share their input -> one
+        64 -> head_conv * len(names) conv"""
+        w0 = torch.cat([sd[h + '.0.weight'] for h in names], 0)
+        return ops.pack_weight(w0), _wino(w0), torch.cat([sd[h + '.0.bias'] for h in names], 0).contiguous()
+
+    def _pack_tail(self, sd, names):
+        """(packed weight, bias) of the 1x1 output layer of one head"""
+        h, = names
+        return ops.pack_weight(sd[h + '.2.weight']), sd[h + '.2.bias'].contiguous()
+
+    def _pack_block_diag(self, sd, names):
+        """(packed weight, bias) of all second (1x1) layers as ONE block-diagonal head_conv*nh -> sum(c) conv: a single
+        launch reads the intermediate once and writes every head into channel slices of one NCHW tensor"""
+        w2 = torch.block_diag(*[sd[h + '.2.weight'][:, :, 0, 0] for h in names])[:, :, None, None].contiguous()
+        return ops.pack_weight(w2), torch.cat([sd[h + '.2.bias'] for h in names], 0).contiguous()
+
+    def _pack_fused(self, sd, names):
+        """(w0 Winograd-packed, b0, w2 [n,8,256], b2 [n,8]) of ct_heads_fused for the heads ``names``"""
+        hc = self.head_conv
+        dev = sd[names[0] + '.2.weight'].device
+        w0s = torch.cat([sd[h + '.0.weight'] for h in names], 0)
+        w2s = torch.zeros((len(names), 8, hc), device=dev)
+        b2s = torch.zeros((len(names), 8), device=dev)
+        for i, h in enumerate(names):
+            c = self.heads[h]
+            w2s[i, :c] = sd[h + '.2.weight'].reshape(c, hc)
+            b2s[i, :c] = sd[h + '.2.bias']
+        return (ops.pack_winograd(w0s), torch.cat([sd[h + '.0.bias'] for h in names], 0).contiguous(),
+                w2s.contiguous(), b2s.contiguous())
+
+    def _pack_point(self, sd, names):
+        """one sparse head (_point_heads): direct-form packed conv3x3 weights (the Winograd form has no single-pixel
+        evaluation), hidden bias, [c, 256] output layer, output bias"""
+        h, = names
+        c, hc = self.heads[h], self.head_conv
+        return (ops.pack_weight(sd[h + '.0.weight']), sd[h + '.0.bias'].contiguous(),
+                sd[h + '.2.weight'].reshape(c, hc).contiguous(), sd[h + '.2.bias'].contiguous())
+
+    def _dense_split(self):
+        """(small, big): heads with <= 8 output channels go into ONE launch for conv3x3 + ReLU + conv1x1 of all of them
+        (ct_heads_fused: Winograd, head_conv 256); the remaining (wide) heads keep the two-launch form on their own
+        channels.  ('hm_hp' stays out whatever its width: ct_heads_fused has ONE sigmoid range, taken by 'hm'; the
+        per-head 1x1 tail applies hm_hp's sigmoid, detector.py:300-304)"""
+        ok = WINOGRAD and self.head_conv == 256
+        small = [h for h, c in self.heads.items() if ok and c <= 8 and h != 'hm_hp'][:_lib.CT_MAX_FUSED_HEADS]
+        return small, [h for h in self.heads if h not in small]
+
+    def _point_heads(self):
+        """sparse heads (round 5, opt-in): the heads that can be evaluated at single pixels -- the regression heads the
+        decode only reads at the K winners, hps and the joint offset head of the pose task; head_conv 256 only"""
+        return [h for h in self.heads if self.head_conv == 256 and (h in _lib.HEAD_INDEX or h in ('hps', 'hp_offset'))]
+
+    def _winner_heads(self, feat):
         """``plan['sparse']``: the regression heads ct_decode evaluates at the K winners (ct_sparse_heads_desc), None if there
         are none.  Dead heads are left out: generic_decode overwrites the wh box with the ltrb / ltrb_amodal box
         (decode.py:131-139,150-159) and `reg` only feeds the wh box (decode.py:102-110) -- neither reaches the returned dict,
         so with the MOT head set (opts.py:343-359 + --ltrb_amodal) they are not evaluated at all"""
-        sp = [h for h in self.heads if h in _lib.HEAD_INDEX and ('sparse.' + h) in P]
+        sp = [h for h in self._point_heads() if h in _lib.HEAD_INDEX]
         if {'ltrb', 'ltrb_amodal'} & set(self.heads):
             sp = [h for h in sp if h not in ('reg', 'wh')]
-        return {'feat': feat, 'heads': [(h,) + P['sparse.' + h] for h in sp], 'depth_scale': self.depth_scale} if sp else None
+        heads = [(h,) + self._packed('point', [h]) for h in sp]
+        return {'feat': feat, 'heads': heads, 'depth_scale': self.depth_scale} if sp else None
 
+    # --- the plan: every launch of a frame, built in stages ------------------------------------------------
     def _build_plan(self, N, H, W, with_img, with_hm, fuse_sigmoid, sparse_heads=False, sparse_pose=False, *, trunk_only=False):
         """``sparse_pose`` (opt-in, pose head sets): hm and hm_hp are the only dense head launches; reg / wh or ltrb / tracking
         go to ``plan['sparse']`` like ``sparse_heads``, hps and the offset head to ``plan['sparse_pose']``.
         ``trunk_only``: the plan stops at ``plan['feat']``, the 64-channel feature map, and has no head launches
         (heads.HeadFinetuner trains the heads on it)"""
         P = self._prepare()
-        lib = _lib.load()
         dev = next(self.buffers()).device
         if H % 32 or W % 32:
             raise _lib.CTError('input %dx%d must be a multiple of 32 (reference pads to 32 too, opts.py:297)' % (H, W))
-        plan = {'launches': [], 'ws_need': 0}
-        L = plan['launches']
-        tune = autotune.enabled()
-
-        def alloc(h, w, c):
-            return ops.new_view(N, h, w, c, dev)
-
-        def add_conv(name, x, pk, cout, ks, stride=1, relu=True, res=None, out=None, **kw):
-            wp, sc, sh, ww = pk
-            d = ops.make_conv_desc(x, wp, cout, ks, stride, scale=sc, shift=sh, res=res, relu=relu, out=out,
-                                   w_wino=(ww if stride == 1 else None), **kw)
-            us = autotune.tune_conv(d, dev)[2] if tune else 10.0
-            L.append(_Launch(name, 'conv', d, (x, res, out, pk, kw.get('out_nchw'), kw.get('pool'), kw.get('proj')), reads=(x, res),
-                             writes=(out, kw.get('out_nchw')), us=us,
-                             ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-            return out
-
+        b = _Builder(N, dev, autotune.enabled())
         # static inputs (copied into before each replay)
         x_in = torch.zeros((N, 3, H, W), device=dev)
         img_in = torch.zeros((N, 3, H, W), device=dev) if with_img else None
         hm_in = torch.zeros((N, 1, H, W), device=dev) if with_hm else None
-        plan['inputs'] = (x_in, img_in, hm_in)
-        s0 = alloc(H, W, 16)
-        L.append(_Launch('stem', 'stem', (x_in, img_in, hm_in, s0), (), reads=(x_in, img_in, hm_in), writes=(s0,), us=46.0))
-        l0 = add_conv('level0', s0, P['level0'], 16, 3, out=alloc(H, W, 16))
-        l1 = add_conv('level1', l0, P['level1'], 32, 3, stride=2, out=alloc(H // 2, W // 2, 32))
+        plan = {'launches': b.launches, 'inputs': (x_in, img_in, hm_in)}
+        feats = self._plan_trunk(b, P, plan['inputs'], H, W)
+        feat, plan['dcn_knobs'], plan['dcn_layers'] = self._plan_neck(b, P, feats, H, W)
+        plan['feat'] = feat
+        plan['sparse'], plan['sparse_pose'], plan['outputs'] = self._plan_heads(b, feat, fuse_sigmoid, sparse_heads,
+                                                                               sparse_pose, trunk_only)
+        ws = _share_conv_workspace(b.launches, dev)
+        plan['ws'], plan['ws_need'] = [ws], ws.numel() * 4
+        return plan
 
-        def leaf(name, x, pk, cin, cout, stride, R, out, bottom=None, level_root=False, make_bottom=False):
-            """Tree(levels=1).forward (dla.py:215-228) over the concat buffer R = [x2 | x1 | children].  ``bottom`` =
-            Tree.downsample(x) (dla.py:207,217): a 2x2 max-pool that (round 3) tree1.conv1 -- the 3x3 stride-2 conv over
-            the same x -- writes as a side output of its launch instead of a launch of its own (``make_bottom``: the
-            caller owns the buffer and wants it filled here)."""
-            h, w = x.H // stride, x.W // stride
-            fold = None
-            # round 4: Tree.project (conv1x1 + BN of the pooled input, dla.py:196-203,217-218) is a second output of the
-            # tree1.conv1 launch -- same input patches, the pooling window is four taps of the 3x3 stride-2 window
-            fuse_proj = FUSE_PROJ and stride == 2 and cin != cout
-            if stride > 1 and bottom is None:
-                if level_root:
-                    bottom = R.slice(2 * cout, cin)
-                    make_bottom = True
-                elif not fuse_proj:
-                    bottom = alloc(h, w, cin)
-                    make_bottom = True
-                # (else: the pooled tensor only feeds the projection and is never materialised)
-            elif stride == 1:
-                bottom = x
-            if stride > 1 and make_bottom:
-                if FOLD_POOL:
-                    fold = bottom
-                else:
-                    L.append(_Launch(name + '.pool', 'pool', (x, bottom), reads=(x,), writes=(bottom,)))
-            t = alloc(h, w, cout)
-            x1 = R.slice(cout, cout)
-            x2 = R.slice(0, cout)
-            if fuse_proj:
-                residual = alloc(h, w, cout)
-                add_conv(name + '.t1.conv1+project', x, pk['c11'], cout, 3, stride=stride, out=t, pool=fold,
-                         proj=(pk['proj'][0], pk['proj'][1], pk['proj'][2], residual))
-            else:
-                add_conv(name + '.t1.conv1', x, pk['c11'], cout, 3, stride=stride, out=t, pool=fold)
-                if cin != cout:
-                    residual = add_conv(name + '.project', bottom, pk['proj'], cout, 1, relu=False, out=alloc(h, w, cout))
-                else:
-                    residual = bottom
-            add_conv(name + '.t1.conv2', t, pk['c12'], cout, 3, res=residual, out=x1)
-            add_conv(name + '.t2.conv1', x1, pk['c21'], cout, 3, out=t)
-            add_conv(name + '.t2.conv2', t, pk['c22'], cout, 3, res=x1, out=x2)
-            add_conv(name + '.root', View(R.buf, R.c0, R.C), pk['root'], cout, 1, out=out)
-            return out
-
+    def _plan_trunk(self, b, P, inputs, H, W):
+        """The stems (dla.py:305-311, one launch), level0 / level1 and the four tree levels of DLA-34: returns the six
+        level outputs."""
+        x_in, img_in, hm_in = inputs
+        s0 = b.alloc(H, W, 16)
+        b.launches.append(_Launch('stem', 'stem', (x_in, img_in, hm_in, s0), out=s0))
+        l0 = b.conv_bn('level0', s0, P['level0'], 16, 3, out=b.alloc(H, W, 16))
+        l1 = b.conv_bn('level1', l0, P['level1'], 32, 3, stride=2, out=b.alloc(H // 2, W // 2, 32))
         feats = [l0, l1]
-        x = l1
         for i in range(2, 6):
+            x = feats[-1]
             p = 'base.level%d' % i
             cin, cout = CHANNELS[i - 1], CHANNELS[i]
             h, w = x.H // 2, x.W // 2
-            out = alloc(h, w, cout)
+            out = b.alloc(h, w, cout)
             level_root = i >= 3
             if LEVELS[i] == 1:
-                R = alloc(h, w, 2 * cout + (cin if level_root else 0))
-                leaf(p, x, P[p], cin, cout, 2, R, out, level_root=level_root)
+                R = b.alloc(h, w, 2 * cout + (cin if level_root else 0))
+                self._plan_leaf(b, p, x, P[p], cin, cout, 2, R, out, level_root=level_root)
             else:
                 # Tree(levels=2): R2 = [y2 | y1 | bottom | x1]; the outer project is dead code (dla.py:218)
-                R2 = alloc(h, w, 3 * cout + cin)
+                R2 = b.alloc(h, w, 3 * cout + cin)
                 bottom = R2.slice(2 * cout, cin)
                 x1 = R2.slice(2 * cout + cin, cout)
-                R1 = alloc(h, w, 2 * cout)
-                leaf(p + '.tree1', x, P[p + '.tree1'], cin, cout, 2, R1, x1, bottom=bottom, make_bottom=True)
-                leaf(p + '.tree2', x1, P[p + '.tree2'], cout, cout, 1, R2, out)
+                R1 = b.alloc(h, w, 2 * cout)
+                self._plan_leaf(b, p + '.tree1', x, P[p + '.tree1'], cin, cout, 2, R1, x1, bottom=bottom, make_bottom=True)
+                self._plan_leaf(b, p + '.tree2', x1, P[p + '.tree2'], cout, cout, 1, R2, out)
             feats.append(out)
-            x = out
+        return feats
 
+    def _plan_leaf(self, b, name, x, pk, cin, cout, stride, R, out, bottom=None, level_root=False, make_bottom=False):
+        """Tree(levels=1).forward (dla.py:215-228) over the concat buffer R = [x2 | x1 | children].  ``bottom`` =
+        Tree.downsample(x) (dla.py:207,217): a 2x2 max-pool that (round 3) tree1.conv1 -- the 3x3 stride-2 conv over
+        the same x -- writes as a side output of its launch instead of a launch of its own (``make_bottom``: the
+        caller owns the buffer and wants it filled here)."""
+        h, w = x.H // stride, x.W // stride
+        # round 4: Tree.project (conv1x1 + BN of the pooled input, dla.py:196-203,217-218) is a second output of the
+        # tree1.conv1 launch -- same input patches, the pooling window is four taps of the 3x3 stride-2 window
+        fuse_proj = FUSE_PROJ and stride == 2 and cin != cout
+        if stride > 1 and bottom is None:
+            if level_root:
+                bottom = R.slice(2 * cout, cin)
+                make_bottom = True
+            elif not fuse_proj:
+                bottom = b.alloc(h, w, cin)
+                make_bottom = True
+            # (else: the pooled tensor only feeds the projection and is never materialised)
+        elif stride == 1:
+            bottom = x
+        pool = bottom if (stride > 1 and make_bottom) else None
+        t = b.alloc(h, w, cout)
+        x1 = R.slice(cout, cout)
+        x2 = R.slice(0, cout)
+        if fuse_proj:
+            residual = b.alloc(h, w, cout)
+            b.conv_bn(name + '.t1.conv1+project', x, pk['c11'], cout, 3, stride=stride, out=t, pool=pool,
+                      proj=(pk['proj'][0], pk['proj'][1], pk['proj'][2], residual))
+        else:
+            b.conv_bn(name + '.t1.conv1', x, pk['c11'], cout, 3, stride=stride, out=t, pool=pool)
+            if cin != cout:
+                residual = b.conv_bn(name + '.project', bottom, pk['proj'], cout, 1, relu=False, out=b.alloc(h, w, cout))
+            else:
+                residual = bottom
+        b.conv_bn(name + '.t1.conv2', t, pk['c12'], cout, 3, res=residual, out=x1)
+        b.conv_bn(name + '.t2.conv1', x1, pk['c21'], cout, 3, out=t)
+        b.conv_bn(name + '.t2.conv2', t, pk['c22'], cout, 3, res=x1, out=x2)
+        return b.conv_bn(name + '.root', View(R.buf, R.c0, R.C), pk['root'], cout, 1, out=out)
+
+    def _plan_neck(self, b, P, feats, H, W):
+        """DLAUp.forward (dla.py:568-574) and the IDAUp of DLASeg.imgpre2feats (dla.py:631-640) over the level outputs:
+        records the 16 DeformConv nodes, has them scheduled together and returns (the 64-channel feature view, the DCN
+        schedule knobs, {node name: result view})."""
         dcn_layers, dcn_views = [], {}
 
         def deform(name, x, cout, out, up=None):
@@ -357,10 +397,10 @@ class DLASegHIP(torch.nn.Module):
                 k = i - startp
                 f = up_f[k]
                 xi = layers[i]
-                up = alloc(xi.H * f, xi.W * f, o)
-                deform('%s.proj_%d' % (p, k), xi, o, alloc(xi.H, xi.W, o),
+                up = b.alloc(xi.H * f, xi.W * f, o)
+                deform('%s.proj_%d' % (p, k), xi, o, b.alloc(xi.H, xi.W, o),
                        up=(P['%s.up_%d' % (p, k)], f, layers[i - 1], up))
-                layers[i] = deform('%s.node_%d' % (p, k), up, o, alloc(up.H, up.W, o))
+                layers[i] = deform('%s.node_%d' % (p, k), up, o, b.alloc(up.H, up.W, o))
 
         layers = list(feats)                                   # DLAUp.forward, dla.py:568-574
         outs = [layers[-1]]
@@ -369,145 +409,107 @@ class DLASegHIP(torch.nn.Module):
         ida('dla_up.ida_2', layers, 2, 6, 64, [1, 2, 2, 2]); outs.insert(0, layers[-1])
         y = [outs[0], outs[1], outs[2]]                        # DLASeg.imgpre2feats, dla.py:631-640
         ida('ida_up', y, 0, 3, 64, [1, 2, 4])
-        feat = y[-1]
-        plan['feat'] = feat
-        knobs, dcn_launches = self._tune_dcn_schedule(dcn_layers, dcn_views, N, H, W, dev, tune)
-        plan['dcn_knobs'] = knobs
-        plan['dcn_layers'] = {v.name: (v.up[3] if v.up is not None else v.out) for v in dcn_views.values()}   # name -> result view
-        L.extend(dcn_launches)
+        knobs, dcn_launches = self._tune_dcn_schedule(dcn_layers, dcn_views, b.N, H, W, b.dev, b.tune)
+        b.launches.extend(dcn_launches)
+        return y[-1], knobs, {v.name: (v.up[3] if v.up is not None else v.out) for v in dcn_views.values()}   # name -> result view
 
-        small, big = P['heads_small'], P['heads_big']
-        plan['sparse'] = plan['sparse_pose'] = None
+    def _plan_heads(self, b, feat, fuse_sigmoid, sparse_heads, sparse_pose, trunk_only):
+        """Which heads are computed as maps and which at points: returns (``plan['sparse']``, ``plan['sparse_pose']``,
+        the dense outputs) and appends the dense head launches (_plan_dense_heads)."""
+        small, big = self._dense_split()
+        point = self._point_heads()
+        sparse = pose = None
         if sparse_pose:
             # hps is read at the K winners and the offset head at the K peaks of each joint map (decode.py:161-167, 21-28):
-            # ct_decode_pose_sparse evaluates them there.  hm keeps the launch form of the sparse plans ('hs:hm'), hm_hp its
-            # dense form (conv3x3 + 1x1 tail with the sigmoid), so winners and peaks are the dense path's
+            # ct_decode_pose_sparse evaluates them there.  hm keeps the launch form of the sparse plans (fused, alone), hm_hp
+            # its dense form (conv3x3 + 1x1 tail with the sigmoid), so winners and peaks are the dense path's
             hs = set(self.heads)
-            if (sparse_heads or not {'hm', 'hps', 'hm_hp'} <= hs or 'ltrb_amodal' in hs or 'sparse.hps' not in P or not fuse_sigmoid
+            if (sparse_heads or not {'hm', 'hps', 'hm_hp'} <= hs or 'ltrb_amodal' in hs or 'hps' not in point or not fuse_sigmoid
                     or 'hm' not in small or 'hm_hp' not in big):
                 raise _lib.CTError('sparse pose heads need hm, hps and hm_hp heads with head_conv 256, no ltrb_amodal head '
                                    '(the match finds its gate box in the packed row) and the detector\'s fused epilogues')
-            plan['sparse'] = self._winner_heads(P, feat)
+            sparse = self._winner_heads(feat)
             off = 'hp_offset' if 'hp_offset' in hs else 'reg' if 'reg' in hs else None
-            plan['sparse_pose'] = {'feat': feat, 'hps': P['sparse.hps'], 'off': P['sparse.' + off] if off else None}
+            pose = {'feat': feat, 'hps': self._packed('point', ['hps']), 'off': self._packed('point', [off]) if off else None}
             small, big = ['hm'], ['hm_hp']
         if sparse_heads:
             # opt-in (detector only, never Module.forward): the regression heads the decode reads at the K winners are not
             # computed as maps -- ct_decode evaluates them at those pixels (ct_sparse_heads_desc)
-            plan['sparse'] = self._winner_heads(P, feat)
-            if plan['sparse'] is None or 'hm' not in self.heads or {'hps', 'hm_hp'} & set(self.heads) or not fuse_sigmoid:
+            sparse = self._winner_heads(feat)
+            if sparse is None or 'hm' not in self.heads or {'hps', 'hm_hp'} & set(self.heads) or not fuse_sigmoid:
                 raise _lib.CTError('sparse heads need an hm head, regression heads with head_conv 256, no pose heads '
                                    'and the detector\'s fused epilogues')
-            small = [h for h in small if not (h in _lib.HEAD_INDEX and ('sparse.' + h) in P)]          # (the dead heads leave the dense launch too)
-            if any(h in _lib.HEAD_INDEX and ('sparse.' + h) in P for h in big):          # (more small heads than one fused launch holds: not with sparse heads)
-                raise _lib.CTError('sparse heads: %s do not fit the fused-heads launch' % [h for h in big if ('sparse.' + h) in P])
+            small = [h for h in small if not (h in _lib.HEAD_INDEX and h in point)]          # (the dead heads leave the dense launch too)
+            if any(h in _lib.HEAD_INDEX and h in point for h in big):          # (more small heads than one fused launch holds: not with sparse heads)
+                raise _lib.CTError('sparse heads: %s do not fit the fused-heads launch' % [h for h in big if h in point])
         if trunk_only:
             if sparse_heads or sparse_pose:
                 raise _lib.CTError('a trunk-only plan has no heads, sparse or dense')
-            outputs = OrderedDict()
-        elif small or plan['sparse'] is not None:
-            outputs = self._plan_heads_fused(plan, L, P, feat, N, dev, tune, fuse_sigmoid, small, big)
-        else:
-            nh = len(self.heads)
-            hc = self.head_conv
-            mid = alloc(feat.H, feat.W, hc * nh)
-            d = ops.make_conv_desc(feat, P['head0_w'], hc * nh, 3, 1, shift=P['head0_b'], relu=True, out=mid,
-                                   w_wino=P['head0_ww'])
-            us = autotune.tune_conv(d, dev)[2] if tune else 200.0
-            L.append(_Launch('heads.0', 'conv', d, (feat, mid), reads=(feat,), writes=(mid,), us=us,
-                             ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-            ctot = sum(self.heads.values())
-            comb = torch.empty((N, ctot, feat.H, feat.W), device=dev)
-            sig, dep = (0, 0), (0, 0)
-            c0 = 0
-            outputs = OrderedDict()
-            for hname, c in self.heads.items():
-                if fuse_sigmoid and hname == 'hm':                 # (hm_hp -> per-head tail below: one sigmoid range per launch)
-                    sig = (c0, c0 + c)
-                if fuse_sigmoid and hname == 'dep':
-                    dep = (c0, c0 + c)
-                outputs[hname] = comb[:, c0:c0 + c]            # channel-slice views of the combined tensor
-                c0 += c
-            if ctot <= 32 and 'hm_hp' not in self.heads:
-                # few output channels (MOT 11, KITTI 9, nuScenes 30): one block-diagonal conv over the whole intermediate
-                d = ops.make_conv_desc(mid, P['head2_w'], ctot, 1, 1, shift=P['head2_b'], out_nchw=comb, sig=sig, dep=dep,
-                                       depth_scale=self.depth_scale)
-                us = autotune.tune_conv(d, dev)[2] if tune else 20.0
-                L.append(_Launch('heads.2', 'conv', d, (mid, comb), reads=(mid,), writes=(comb,), us=us,
-                                 ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-            else:
-                # a wide head (COCO: 80 classes): the block-diagonal form would multiply its flops by the number of heads
-                outputs = OrderedDict()
-                for j, (hname, c) in enumerate(self.heads.items()):
-                    o = torch.empty((N, c, feat.H, feat.W), device=dev)
-                    wp, b = P[hname + '.2']
-                    hsig = (0, c) if (fuse_sigmoid and hname in ('hm', 'hm_hp')) else (0, 0)   # detector.py:300-304
-                    hdep = (0, c) if (fuse_sigmoid and hname == 'dep') else (0, 0)
-                    d = ops.make_conv_desc(mid.slice(hc * j, hc), wp, c, 1, 1, shift=b, out_nchw=o, sig=hsig, dep=hdep,
-                                           depth_scale=self.depth_scale)
-                    us = autotune.tune_conv(d, dev)[2] if tune else 7.0
-                    L.append(_Launch('heads.%s.2' % hname, 'conv', d, (mid, o), reads=(mid.slice(hc * j, hc),), writes=(o,),
-                                     us=us, ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-                    outputs[hname] = o
-        plan['outputs'] = outputs
-        # split-K partials of the dense convs: one workspace shared by all of them (the launches of a frame are
-        # sequential); every DCN layer owns its workspace (the layers of a group run concurrently)
-        need = max([l.ws_need for l in L if l.fn == 'conv'] + [16])
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        plan['ws'] = [ws]
-        for l in L:
-            if l.fn == 'conv':
-                l.args.workspace, l.args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        plan['ws_need'] = ws.numel() * 4
-        return plan
+            return sparse, pose, OrderedDict()
+        return sparse, pose, self._plan_dense_heads(b, feat, fuse_sigmoid, small, big)
 
-    def _plan_heads_fused(self, plan, L, P, feat, N, dev, tune, fuse_sigmoid, small, big):
-        """Heads (base_model.py:24-65,86-90): every head with <= 8 output channels in ONE ct_heads_fused launch (hidden
-        256-channel maps stay in the workgroups); wider heads (80-class hm, hps, hm_hp) as conv3x3 + per-head conv1x1."""
-        lib = _lib.load()
-        hc = self.head_conv
+    def _plan_dense_heads(self, b, feat, fuse_sigmoid, small, big):
+        """Heads (base_model.py:24-65,86-90): every head of ``small`` in ONE ct_heads_fused launch (hidden 256-channel maps
+        stay in the workgroups); the heads of ``big`` (80-class hm, hps, hm_hp; all of them without a fused launch) as one
+        conv3x3 for all their first layers, then their 1x1 output layers."""
+        N, dev, hc = b.N, b.dev, self.head_conv
         outputs = {}
+
+        def channels(names, comb):
+            """the outputs of ``names`` as channel-slice views of the combined tensor; returns ({head: channel range},
+            the `sig` and the `dep` range of the launch that writes it).  'hm' takes the sigmoid range: there is one per
+            launch, hm_hp -> its per-head tail"""
+            rng, c0 = {}, 0
+            for h in names:
+                rng[h] = (c0, c0 + self.heads[h])
+                outputs[h] = comb[:, c0:c0 + self.heads[h]]
+                c0 += self.heads[h]
+            on = rng if fuse_sigmoid else {}
+            return rng, on.get('hm', (0, 0)), on.get('dep', (0, 0))
+
         if small:
             ctot = sum(self.heads[h] for h in small)
             comb = torch.empty((N, ctot, feat.H, feat.W), device=dev)
             hd = _lib.HeadsDesc()
             hd.x, hd.N, hd.H, hd.W, hd.Cin, hd.ldx = feat.ptr, N, feat.H, feat.W, feat.C, feat.ld
-            hs_w0, hs_b0, hs_w2, hs_b2 = P['hs:' + ','.join(small)]
+            pack = hs_w0, hs_b0, hs_w2, hs_b2 = self._packed('fused', small)
             hd.w0_winograd, hd.b0, hd.nheads = hs_w0.data_ptr(), hs_b0.data_ptr(), len(small)
             hd.w2, hd.b2, hd.out, hd.ctot = hs_w2.data_ptr(), hs_b2.data_ptr(), comb.data_ptr(), ctot
             hd.depth_scale = self.depth_scale
-            c0 = 0
+            rng, (hd.sig_lo, hd.sig_hi), (hd.dep_lo, hd.dep_hi) = channels(small, comb)
             for i, h in enumerate(small):
-                c = self.heads[h]
-                hd.cout[i], hd.coff[i] = c, c0
-                if fuse_sigmoid and h == 'hm':
-                    hd.sig_lo, hd.sig_hi = c0, c0 + c
-                if fuse_sigmoid and h == 'dep':
-                    hd.dep_lo, hd.dep_hi = c0, c0 + c
-                outputs[h] = comb[:, c0:c0 + c]
-                c0 += c
-            L.append(_Launch('heads.fused[%s]' % ' + '.join(small), 'heads', hd, (feat, comb, hs_w0, hs_b0, hs_w2, hs_b2),
-                             us=100.0))
+                hd.cout[i], hd.coff[i] = self.heads[h], rng[h][0]
+            b.launches.append(_Launch('heads.fused[%s]' % ' + '.join(small), 'heads', hd, (feat, comb) + pack, out=comb))
         if big:
-            mid = ops.new_view(N, feat.H, feat.W, hc * len(big), dev)
-            sfx = '' if big == P['heads_big'] else ':' + ','.join(big)      # (a sparse-pose plan keeps hm_hp alone)
-            d = ops.make_conv_desc(feat, P['hb_w' + sfx], hc * len(big), 3, 1, shift=P['hb_b' + sfx], relu=True, out=mid,
-                                   w_wino=P['hb_ww' + sfx])
-            us = autotune.tune_conv(d, dev)[2] if tune else 100.0
-            L.append(_Launch('heads.0', 'conv', d, (feat, mid), us=us, ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-            for j, h in enumerate(big):
-                c = self.heads[h]
-                o = torch.empty((N, c, feat.H, feat.W), device=dev)
-                wp, b = P[h + '.2']
-                hsig = (0, c) if (fuse_sigmoid and h in ('hm', 'hm_hp')) else (0, 0)       # detector.py:300-304
-                hdep = (0, c) if (fuse_sigmoid and h == 'dep') else (0, 0)
-                d = ops.make_conv_desc(mid.slice(hc * j, hc), wp, c, 1, 1, shift=b, out_nchw=o, sig=hsig, dep=hdep,
-                                       depth_scale=self.depth_scale)
-                us = autotune.tune_conv(d, dev)[2] if tune else 7.0
-                L.append(_Launch('heads.%s.2' % h, 'conv', d, (mid, o), us=us,
-                                 ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d))))
-                outputs[h] = o
+            wp, ww, b0 = pack = self._packed('first', big)
+            mid = b.alloc(feat.H, feat.W, hc * len(big))
+            b.conv('heads.0', ops.make_conv_desc(feat, wp, hc * len(big), 3, 1, shift=b0, relu=True, out=mid, w_wino=ww),
+                   (feat, mid, pack), mid)
+            ctot = sum(self.heads[h] for h in big)
+            if big == list(self.heads) and ctot <= 32 and 'hm_hp' not in big:
+                # every head is here (no fused launch, none evaluated at points) and they have few output channels (MOT 11,
+                # KITTI 9, nuScenes 30): one block-diagonal conv over the whole intermediate
+                comb = torch.empty((N, ctot, feat.H, feat.W), device=dev)
+                _, sig, dep = channels(big, comb)
+                wp, b2 = pack = self._packed('block_diag', big)
+                b.conv('heads.2', ops.make_conv_desc(mid, wp, ctot, 1, 1, shift=b2, out_nchw=comb, sig=sig, dep=dep,
+                                                     depth_scale=self.depth_scale), (mid, comb, pack), comb)
+            else:
+                # a wide head (COCO: 80 classes): the block-diagonal form would multiply its flops by the number of heads
+                for j, h in enumerate(big):
+                    outputs[h] = self._plan_head_tail(b, h, mid.slice(hc * j, hc), fuse_sigmoid)
         return OrderedDict((h, outputs[h]) for h in self.heads if h in outputs)
+
+    def _plan_head_tail(self, b, h, hidden, fuse_sigmoid):
+        """`heads.<h>.2`: the 1x1 output layer of one head over its ``hidden`` slice of the first layers' output, into
+        an NCHW tensor of its own, with the head's own sigmoid / depth range"""
+        c = self.heads[h]
+        o = torch.empty((b.N, c, hidden.H, hidden.W), device=b.dev)
+        wp, b2 = pack = self._packed('tail', [h])
+        hsig = (0, c) if (fuse_sigmoid and h in ('hm', 'hm_hp')) else (0, 0)       # detector.py:300-304
+        hdep = (0, c) if (fuse_sigmoid and h == 'dep') else (0, 0)
+        d = ops.make_conv_desc(hidden, wp, c, 1, 1, shift=b2, out_nchw=o, sig=hsig, dep=hdep, depth_scale=self.depth_scale)
+        return b.conv('heads.%s.2' % h, d, (hidden, o, pack), o)
 
     def run_stem_partial(self, x, pre_img, out):
         """the terms of the stem that do not depend on the tracker (dla.py:305-311: base_layer(x) + pre_img_layer(
@@ -539,9 +541,6 @@ class DLASegHIP(torch.nn.Module):
                 rc = lib.ct_dcn_v2_group(arr, n, phases, st)
             elif l.fn == 'heads':
                 rc = lib.ct_heads_fused(ctypes.byref(l.args), st)
-            elif l.fn == 'pool':
-                x, y = l.args
-                rc = lib.ct_maxpool2x2(x.ptr, x.N, x.H, x.W, x.C, x.ld, y.ptr, y.ld, st)
             elif l.fn == 'stem':
                 x, img, hm, y = l.args
                 if inputs is not None:
@@ -588,10 +587,7 @@ class DLASegHIP(torch.nn.Module):
                 else:
                     om = omv
                     d = ops.make_conv_desc(x, pk['w_off'], 27, 3, 1, shift=pk['b_off'], out=om, sig=(18, 27))
-                if tune:
-                    autotune.tune_conv(d, dev)
-                convs[name] = _Launch(name + '.offset', 'conv', d, (x, omv, pk),
-                                      ws_need=lib.ct_conv2d_workspace_bytes(ctypes.byref(d)))
+                convs[name] = _conv_launch(name + '.offset', d, (x, omv, pk), omv, dev, tune)
             elif p.src != 'fused':                   # ('parts' / 'wino': written by the slot's OFFSETS launch)
                 part = torch.empty((x.C // 64) * N * x.H * x.W * 32, dtype=torch.float32, device=dev)
             own = p.src != 'map'
@@ -627,13 +623,8 @@ class DLASegHIP(torch.nn.Module):
     def _time_launches(self, launches, reps=10):
         """device time (us) of a launch list, by graph replay on a side stream"""
         plan = {'launches': launches}
-        need = max([l.ws_need for l in launches if l.fn == 'conv'] + [16])
-        dev = next(self.buffers()).device
-        ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        for l in launches:
-            if l.fn == 'conv':
-                l.args.workspace, l.args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        side = torch.cuda.Stream()
+        ws = _share_conv_workspace(launches, next(self.buffers()).device)       # (alive until the timing is done)
+        side =torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             self._run_plan(plan)
