@@ -347,7 +347,7 @@ CT_OPTIM_MAX_TENSORS = 1 << 20
 class OptimRec(ctypes.Structure):
     _fields_ = [('p', ctypes.c_void_p), ('g', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p),
                 ('numel', ctypes.c_longlong), ('s', ctypes.c_float * CT_OPTIM_SCALARS), ('first', ctypes.c_int),
-                ('reserved', ctypes.c_int * 13)]
+                ('reserved', ctypes.c_int * 11), ('src', ctypes.c_void_p)]
 
 
 class OptimGuard(ctypes.Structure):
@@ -390,7 +390,7 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
            'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials',
            'ct_optim_step', 'ct_slot_gather', 'ct_slot_fold',
-           'ct_optim_norms_workspace_bytes', 'ct_optim_norms', 'ct_optim_step_guarded']
+           'ct_optim_norms_workspace_bytes', 'ct_optim_norms', 'ct_optim_step_guarded', 'ct_optim_pack_grads']
 
 _lib = None
 
@@ -555,6 +555,7 @@ def load():
     lib.ct_optim_norms_workspace_bytes.argtypes = [i, ctypes.c_longlong]
     lib.ct_optim_norms.argtypes = [p, i, ctypes.c_longlong, ctypes.c_double, i, p, p, p, sz, p]
     lib.ct_optim_step_guarded.argtypes = [p, i, ctypes.c_longlong, i, p, p]
+    lib.ct_optim_pack_grads.argtypes = [p, i, ctypes.c_longlong, ctypes.c_float, p]
     lib.ct_slot_gather.argtypes = [ctypes.POINTER(SlotDesc), p]
     lib.ct_slot_fold.argtypes = [ctypes.POINTER(SlotDesc), p]
     # CENTERTRACK_TUNE="key=value,key=value": launch-heuristic knobs of ct_set_tuning (A/B runs)

@@ -8,7 +8,13 @@
 // non-finite counts, then one workgroup that adds them in a fixed order and writes the clip coefficient and the skip
 // decision into ct_optim_guard -- and ct_optim_step_guarded is the step kernel with GUARDED = true, reading both.  Still no
 // atomics; the only LDS is the 96 bytes through which pass 1 adds its four waves.
+//
+// Data-parallel training: ct_optim_pack_grads walks the table once more, in front of the two, and
+// gathers every gradient (rec.src), scaled, into the flat buffer rec.g points into; the replicas all-reduce that buffer
+// and the kernels above read it through rec.g, unchanged.
 #include "ct_common.h"
+
+#include <cstring>
 
 namespace {
 
@@ -291,6 +297,52 @@ __global__ __launch_bounds__(FIN_THREADS) void optim_norms_finish_kernel(const i
     }
 }
 
+// ---- ct_optim_pack_grads -------------------------------------------------------------------------------------------
+// The gather of data-parallel training: g[i] = src[i] * scale over whole chunks of the flat buffer
+// g points into, the tail of a tensor's last chunk written as +0.0.  Lane l owns elements 4 (l + 256 k) + e of a chunk, as
+// in pass 1 of the norms; a chunk of g is 16-byte aligned exactly when the flat buffer is.
+__global__ __launch_bounds__(OPT_THREADS) void optim_pack_kernel(const ct_optim_rec *recs, const int *prefix, int n, float scale)
+{
+    const int total = prefix[n];
+    for (long long cl = blockIdx.x; cl < total; cl += gridDim.x) {
+        const int c = (int)cl;
+        int lo = 0, hi = n;                          // prefix[lo] <= c < prefix[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (prefix[mid] <= c) lo = mid;
+            else hi = mid;
+        }
+        const ct_optim_rec &r = recs[lo];
+        const long long base = (long long)(c - prefix[lo]) * OPT_CHUNK;
+        const long long left = r.numel - base;
+        if (left <= 0 || r.src == nullptr || r.g == nullptr) continue;   // (a table that disagrees with itself: touch nothing)
+        const int cnt = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
+        const float *src = r.src + base;
+        float *g = const_cast<float *>(r.g) + base;
+        const bool vec_in = ((uintptr_t)r.src & 15) == 0, vec_out = ((uintptr_t)r.g & 15) == 0;
+#pragma unroll
+        for (int k = 0; k < NORM_PASSES; ++k) {
+            const int e0 = (threadIdx.x + k * OPT_THREADS) * 4;
+            f32x4 x = {0.f, 0.f, 0.f, 0.f};
+            if (vec_in && e0 + 4 <= cnt) {
+                x = *reinterpret_cast<const f32x4 *>(src + e0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[e] = optim_clip(x[e], scale);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (e0 + e < cnt) x[e] = optim_clip(src[e0 + e], scale);
+            }
+            if (vec_out) {
+                *reinterpret_cast<f32x4 *>(g + e0) = x;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[e0 + e] = x[e];
+            }
+        }
+    }
+}
+
 const char *optim_refuse(const char *who, const void *table, int n, long long chunks, int kind)
 {
     static thread_local char msg[160];
@@ -332,6 +384,20 @@ extern "C" int ct_optim_step_guarded(const void *table, int n, long long chunks,
                                      void *stream)
 {
     return optim_launch<true>("ct_optim_step_guarded", table, n, chunks, kind, guard, stream);
+}
+
+extern "C" int ct_optim_pack_grads(const void *table, int n, long long chunks, float scale, void *stream)
+{
+    if (const char *why = optim_refuse("ct_optim_pack_grads", table, n, chunks, CT_OPTIM_ADAM)) CT_FAIL_ARG("%s", why);
+    unsigned bits;
+    memcpy(&bits, &scale, sizeof bits);
+    if ((bits & 0x7f800000u) == 0x7f800000u) CT_FAIL_ARG("ct_optim_pack_grads: scale %g is not finite", (double)scale);
+    const ct_optim_rec *recs = (const ct_optim_rec *)table;
+    const int *prefix = (const int *)(recs + n);
+    const unsigned grid = (unsigned)(chunks < OPT_MAX_BLOCKS ? chunks : OPT_MAX_BLOCKS);
+    hipLaunchKernelGGL(optim_pack_kernel, dim3(grid), dim3(OPT_THREADS), 0, (hipStream_t)stream, recs, prefix, n, scale);
+    CT_CHECK_LAUNCH("ct_optim_pack_grads");
+    return CT_OK;
 }
 
 extern "C" size_t ct_optim_norms_workspace_bytes(int n, long long chunks)

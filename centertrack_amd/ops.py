@@ -1161,6 +1161,14 @@ def optim_step(table, n, chunks, kind):
     _lib.check(_lib.load().ct_optim_step(table.data_ptr(), n, chunks, kind, _lib.stream_ptr()), 'ct_optim_step')
 
 
+def optim_pack_grads(table, n, chunks, scale):
+    """ct_optim_pack_grads (csrc/optim.hip) on the current stream: one launch that gathers
+    ``src[i] * scale`` of every record of the uploaded ``table`` into the flat buffer its ``g`` points into, the tail of every
+    tensor's last chunk written as +0.0."""
+    _lib.check(_lib.load().ct_optim_pack_grads(table.data_ptr(), n, chunks, float(scale), _lib.stream_ptr()),
+               'ct_optim_pack_grads')
+
+
 def optim_norms_workspace_bytes(n, chunks):
     """bytes of workspace ``optim_norms`` needs for ``n`` tensors in ``chunks`` chunks (0: sizes it refuses)"""
     return int(_lib.load().ct_optim_norms_workspace_bytes(n, chunks))

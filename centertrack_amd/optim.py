@@ -21,6 +21,11 @@ nothing here.
 The guarded step: ``optimizer.guard(max_norm=..., skip_nonfinite=...)`` puts ``ct_optim_norms`` in
 front of the update -- the global gradient norm, ``clip_grad_norm_``'s coefficient and a skip decision for gradients that
 are not finite, all of which stay on the device -- and ``grad_stats()`` reads them back on request.
+
+Data-parallel training: ``optimizer.distribute(group=None)`` puts ``ct_optim_pack_grads`` -- one launch
+that gathers every gradient, scaled by 1 / world, into one flat buffer -- and ONE all-reduce of that buffer in front of the
+unguarded or guarded step, which reads the averaged gradient through the same table.  ``reduced_grads()`` hands the
+averaged gradients out, ``check_in_sync()`` compares the replicas on request.
 """
 import numpy as np
 import torch
@@ -33,7 +38,7 @@ MAX_TENSORS = _lib.CT_OPTIM_MAX_TENSORS
 KINDS = {'adam': _lib.CT_OPTIM_ADAM, 'sgd': _lib.CT_OPTIM_SGD}
 # ct_optim_rec of include/centertrack_hip.h
 REC = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('numel', '<i8'),
-                ('s', '<f4', (_lib.CT_OPTIM_SCALARS,)), ('first', '<i4'), ('reserved', '<i4', (13,))])
+                ('s', '<f4', (_lib.CT_OPTIM_SCALARS,)), ('first', '<i4'), ('reserved', '<i4', (11,)), ('src', '<u8')])
 REC_WORDS = REC.itemsize // 4
 assert REC.itemsize == _lib.CT_OPTIM_REC_BYTES
 
@@ -50,11 +55,12 @@ def table_words(n):
     return n * REC_WORDS + n + 1
 
 
-def pack(kind, items, out=None):
+def pack(kind, items, out=None, src=None):
     """The table ``ct_optim_step`` reads, as int32 words: ``len(items)`` records, then the prefix of chunk starts.
     ``items``: per tensor ``(p, g, m, v, numel, scalars, first)`` -- four device addresses (0: absent), the element
     count, up to eight Python floats and the SGD flag.  ``out``: an int32 numpy array to fill instead of a fresh one.
-    Returns ``(words array, n, chunks)``.  Pure host code."""
+    ``src``: per tensor the device address ``ct_optim_pack_grads`` gathers ``g`` from (the record's last 8 bytes, which
+    stay zero without it).  Returns ``(words array, n, chunks)``.  Pure host code."""
     if kind not in (_lib.CT_OPTIM_ADAM, _lib.CT_OPTIM_SGD):
         raise CTError('optim.pack: kind %r is neither CT_OPTIM_ADAM nor CT_OPTIM_SGD' % (kind,))
     n = len(items)
@@ -76,6 +82,14 @@ def pack(kind, items, out=None):
         raise CTError('optim.pack: a pointer that is not 4-byte aligned')
     if (rec['numel'] <= 0).any():
         raise CTError('optim.pack: a tensor without elements')
+    if src is not None:
+        if len(src) != n:
+            raise CTError('optim.pack: %d source addresses for %d tensors' % (len(src), n))
+        rec['src'] = src
+        if (rec['src'] == 0).any():
+            raise CTError('optim.pack: null source pointer in a record')
+        if (rec['src'] & 3).any():
+            raise CTError('optim.pack: a source pointer that is not 4-byte aligned')
     prefix = np.zeros(n + 1, np.int64)
     np.cumsum((rec['numel'] + (CHUNK - 1)) // CHUNK, out=prefix[1:])
     if prefix[-1] >= 1 << 31:
@@ -88,6 +102,29 @@ def pack(kind, items, out=None):
     out[:n * REC_WORDS] = rec.view(np.int32)
     out[n * REC_WORDS:words] = prefix
     return out, n, int(prefix[-1])
+
+
+def flat_layout(numels):
+    """Where ``ct_optim_pack_grads`` puts the tensors of ``numels`` elements in the flat buffer: ``(offsets, total_elems)``,
+    tensor ``t`` at element ``prefix[t] * CHUNK`` -- the chunk prefix of ``pack`` -- and ``total_elems = chunks * CHUNK``."""
+    numels = np.asarray(numels, np.int64).reshape(-1)
+    if numels.size < 1 or (numels <= 0).any():
+        raise CTError('optim.flat_layout: every tensor has at least one element (got %s)' % (numels.tolist(),))
+    prefix = np.zeros(numels.size + 1, np.int64)
+    np.cumsum((numels + (CHUNK - 1)) // CHUNK, out=prefix[1:])
+    return [int(c) * CHUNK for c in prefix[:-1]], int(prefix[-1]) * CHUNK
+
+
+def reference_pack(grads, scale):
+    """``ct_optim_pack_grads`` restated on the host, for the tests: the flat float32 numpy array that holds ``float32(g) *
+    float32(scale)`` of every gradient at its ``flat_layout`` offset and +0.0 in the tail of every tensor's last chunk"""
+    grads = [np.asarray(g, np.float32).reshape(-1) for g in grads]
+    offsets, total = flat_layout([g.size for g in grads])
+    flat = np.zeros(total, np.float32)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        for off, g in zip(offsets, grads):
+            flat[off:off + g.size] = g * np.float32(scale)
+    return flat
 
 
 def find_tensor(prefix, chunk):
@@ -366,8 +403,137 @@ class _FusedStep(object):
         out['per_tensor'] = np.sqrt(host[GUARD_SLOT:].view(np.float64))
         return out
 
+    def distribute(self, group=None):
+        """Data-parallel training, one process per GPU: every later ``step()`` averages the gradients
+        over the ranks of ``group`` (``None``: the default group of ``torch.distributed``; a group of one rank is allowed)
+        before it updates; returns ``self``.  ``distribute(False)`` restores the local ``step()``.
+
+        A distributed ``step()`` takes the parameters of one device.  It uploads one table, as before, in which every
+        record's gradient pointer leads into ONE flat buffer (``flat_layout``; kept, grown by doubling) and ``src`` to
+        ``p.grad``; ``ct_optim_pack_grads`` gathers ``p.grad * float32(1 / world)`` there in one launch, one ``all_reduce(SUM)``
+        (``parallel.all_reduce_flat``) exchanges the buffer, and the unguarded or guarded step runs on the same table.
+        With a guard, norm, clip coefficient and skip decision are formed from the averaged gradient and are therefore the
+        same on every rank; a NaN or Inf on one rank reaches every rank through the sum, so all ranks skip together.
+        Under ``nccl`` the collective is enqueued on the device and the host waits for nothing; under ``gloo`` the buffer
+        goes through a pinned host block and the host WAITS -- that path is there so that tests and boxes without RCCL run
+        the same code.  ``p.grad`` is not written (the rule of the guard); ``reduced_grads()`` hands out the averaged
+        gradients.
+
+        The tensors that carry a gradient are fixed by the first distributed step: there the ranks compare a hash of
+        their element counts and raise on every rank if they differ, and a later step with another list raises
+        ``CTError`` on its rank before any collective."""
+        if group is False:
+            self.__dict__['_dist'] = None
+            return self
+        from . import parallel
+        if not parallel.group_active():
+            raise CTError('centertrack_amd.optim.%s.distribute: no torch.distributed process group (start one process per '
+                          'GPU with torchrun and call parallel.init_from_env first)' % type(self).__name__)
+        self.__dict__['_dist'] = {'group': group, 'layout': None, 'flat': None, 'device': None, 'last': None}
+        return self
+
+    def _check_layout(self, per_device):
+        """a distributed step: one device, and the element counts the first such step fixed (compared across ranks there)"""
+        d = self.__dict__.get('_dist')
+        if d is None:
+            return
+        who = 'centertrack_amd.optim.%s' % type(self).__name__
+        if len(per_device) != 1:
+            raise CTError('%s: a distributed step takes the gradients of one device (got %s)'
+                          % (who, sorted(str(dev) for dev in per_device) or 'no gradient at all'))
+        numels = tuple(it[4] for items in per_device.values() for it in items)
+        if d['layout'] is None:
+            from . import parallel
+            parallel.check_same_digest(','.join(str(v) for v in numels), 'the list of tensors that carry a gradient',
+                                       d['group'])
+            d['layout'] = numels
+            d['offsets'], d['total'] = flat_layout(numels)
+        elif numels != d['layout']:
+            raise CTError('%s: the tensors that carry a gradient changed after the first distributed step (%d tensors, %d '
+                          'elements then; %d tensors, %d elements now): the layout of the reduced buffer is fixed'
+                          % (who, len(d['layout']), sum(d['layout']), len(numels), sum(numels)))
+
+    def _launch_distributed(self, per_device, d):
+        from . import ops, parallel
+        guard = self.__dict__.get('_guard')
+        ring = self.__dict__.setdefault('_ring', [])
+        (device, items), = per_device.items()
+        offsets, total = d['offsets'], d['total']
+        with torch.cuda.device(device):
+            if d['flat'] is None or d['device'] != device or d['flat'].numel() < total:
+                cap = max(d['flat'].numel() if d['flat'] is not None and d['device'] == device else 0, 1 << 16)
+                while cap < total:
+                    cap *= 2
+                d['flat'], d['device'] = torch.zeros(cap, dtype=torch.float32, device=device), device
+            flat, base = d['flat'][:total], d['flat'].data_ptr()
+            words = table_words(len(items))
+            entry = _staging.take(ring, words, torch.int32)
+            _, n, chunks = pack(self._kind, [it[:1] + (base + 4 * off,) + it[2:] for it, off in zip(items, offsets)],
+                                out=entry['host'].numpy(), src=[it[1] for it in items])
+            stream = torch.cuda.current_stream()
+            if d['last'] is not None and d['last'][0] != stream.cuda_stream:
+                stream.wait_event(d['last'][1])              # (the flat buffer is shared between steps: keep them in order)
+            if guard is not None:
+                b = self._guard_buffers(device, n, chunks, words)
+                if b['last'] is not None and b['last'][0] != stream.cuda_stream:
+                    stream.wait_event(b['last'][1])
+                table = b['table']
+            else:
+                table = torch.empty(words, dtype=torch.int32, device=device)
+            table[:words].copy_(entry['host'][:words], non_blocking=True)
+            world = parallel.world_size(d['group'])
+            ops.optim_pack_grads(table, n, chunks, np.float32(1.0 / world))
+            parallel.all_reduce_flat(flat, d['group'])
+            if guard is not None:
+                ops.optim_norms(table, n, chunks, guard[0], guard[1], b['state'][GUARD_SLOT:], b['state'], b['work'])
+                ops.optim_step_guarded(table, n, chunks, self._kind, b['state'])
+            else:
+                ops.optim_step(table, n, chunks, self._kind)
+            entry['event'].record()
+            d['last'] = (stream.cuda_stream, entry['event'])
+            if guard is not None:
+                b['last'] = d['last']
+
+    def _grad_params(self):
+        return [p for group in self.param_groups for p in group['params'] if p.grad is not None and p.numel() > 0]
+
+    def reduced_grads(self):
+        """The gradients the last distributed ``step()`` applied -- averaged over the ranks, before the guard's clipping --
+        as views into the flat buffer: one per parameter in the optimizer's order, in the parameter's shape, ``None`` for
+        a parameter without a gradient.  Valid until the next ``step()``; no wait."""
+        d = self.__dict__.get('_dist')
+        if d is None or d['flat'] is None or d['layout'] is None:
+            raise CTError('centertrack_amd.optim.%s.reduced_grads: no distributed step has run' % type(self).__name__)
+        with_grad = self._grad_params()
+        if tuple(p.numel() for p in with_grad) != d['layout']:
+            raise CTError('centertrack_amd.optim.%s.reduced_grads: the gradients are not those of the last distributed step'
+                          % type(self).__name__)
+        views = {p: d['flat'][off:off + p.numel()].view(p.shape) for p, off in zip(with_grad, d['offsets'])}
+        return [views.get(p) for group in self.param_groups for p in group['params']]
+
+    def check_in_sync(self):
+        """Compare the parameters across the ranks on request: every rank forms a checksum of its parameters' bits, the
+        checksums are all-gathered, and ``CTError`` is raised on every rank, naming the ranks that differ from rank 0.
+        A read that WAITS."""
+        d = self.__dict__.get('_dist')
+        if d is None:
+            raise CTError('centertrack_amd.optim.%s.check_in_sync: distribute() is off' % type(self).__name__)
+        from . import parallel
+        params = [p for group in self.param_groups for p in group['params'] if p.numel() > 0]
+        with torch.no_grad():
+            sums = torch.stack([p.detach().contiguous().view(torch.int32).to(torch.int64).sum() for p in params])
+            weights = torch.arange(1, len(params) + 1, dtype=torch.int64, device=sums.device)
+            mine = torch.stack([sums.sum(), (sums * weights).sum()])     # (int64 wraps: a checksum)
+        bad = parallel.ranks_that_differ(mine, d['group'])
+        if bad:
+            raise CTError('centertrack_amd.optim.%s.check_in_sync: the parameters of rank(s) %s differ from those of rank 0'
+                          % (type(self).__name__, bad))
+
     def _launch(self, per_device):
         from . import ops
+        d = self.__dict__.get('_dist')
+        if d is not None:
+            return self._launch_distributed(per_device, d)
         guard = self.__dict__.get('_guard')
         if guard is not None:
             return self._launch_guarded(per_device, guard)
@@ -453,6 +619,7 @@ class Adam(_FusedStep, torch.optim.Adam):
                     if t not in scalars:
                         scalars[t] = adam_scalars(t, lr, beta1, beta2, eps, wd)
                     per_device.setdefault(c[2], []).append((c[0], g.data_ptr(), c[8], c[9], c[1], scalars[t], 0))
+            self._check_layout(per_device)
             self._advance(visited)
         except BaseException:
             cache.clear()
@@ -518,6 +685,7 @@ class SGD(_FusedStep, torch.optim.SGD):
                             continue
                     per_device.setdefault(c[2], []).append((c[0], g.data_ptr(), c[4], 0, c[1], scalars, c[5]))
                     c[5] = 0
+            self._check_layout(per_device)
         except BaseException:
             cache.clear()
             raise

@@ -59,23 +59,125 @@ def check_same_plan(signature, what='launch plan'):
     """Every rank hashes ``signature`` (a string that pins the fp32 summation order of its plan: per launch the tile
     shape / algo / split-K, the DCN schedule knobs -- ``DLASegHIP.plan_signature``); the hashes are all-gathered and a
     mismatch raises on EVERY rank, naming the ranks that differ from rank 0.  Returns the hex digest."""
-    digest = hashlib.sha256(signature.encode()).digest()
-    hexd = digest[:8].hex()
-    if not group_active():
-        return hexd
-    world = dist.get_world_size()
-    dev = 'cuda' if dist.get_backend() == 'nccl' else 'cpu'
-    mine = torch.tensor([int.from_bytes(digest[0:7], 'little'), int.from_bytes(digest[7:14], 'little')],
-                        dtype=torch.int64, device=dev)
-    allh = torch.zeros(2 * world, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(allh, mine)
-    allh = allh.view(world, 2).tolist()
-    bad = [r for r in range(world) if allh[r] != allh[0]]
+    hexd, bad = _digest_and_who_differs(signature)
     if bad:
         raise RuntimeError('%s differs between ranks: rank(s) %s built another plan than rank 0 (stale '
                            'CENTERTRACK_TUNE_CACHE / CENTERTRACK_DCN_KNOBS on that rank?); identical fp32 summation '
                            'orders on every rank need identical plans' % (what, bad))
     return hexd
+
+
+# --------------------------------------------------------------------------------------------------
+# Data-parallel training (DESIGN.md section 30): one process per GPU, a full replica each.  The exchange of a training step
+# is ONE all-reduce of the flat gradient buffer ``optim.Adam.distribute`` keeps; the rest below runs at start-up, at the
+# reads ``Trainer`` makes anyway, or on request.
+def world_size(group=None):
+    """ranks of ``group`` (``None``: the default group); 1 without a process group"""
+    return dist.get_world_size(group) if group_active() else 1
+
+
+def _host_backend(group=None):
+    """the group's collectives take host tensors (gloo); under nccl they take device tensors"""
+    return dist.get_backend(group) != 'nccl'
+
+
+def ranks_that_differ(mine, group=None):
+    """All-gather the int64 vector ``mine`` (a digest, a checksum; the same length on every rank) and return the ranks
+    whose vector differs from rank 0's -- the same list on every rank; ``[]`` without a group.  A read that waits."""
+    if not group_active():
+        return []
+    world = dist.get_world_size(group)
+    mine = mine.to(device='cpu' if _host_backend(group) else 'cuda', dtype=torch.int64).reshape(-1)
+    allv = torch.zeros(world * mine.numel(), dtype=torch.int64, device=mine.device)
+    dist.all_gather_into_tensor(allv, mine, group=group)
+    allv = allv.view(world, -1).tolist()
+    return [r for r in range(world) if allv[r] != allv[0]]
+
+
+def _digest_and_who_differs(signature, group=None):
+    """(hex digest of the string ``signature``, the ranks whose digest differs from rank 0's)"""
+    digest = hashlib.sha256(signature.encode()).digest()
+    mine = torch.tensor([int.from_bytes(digest[0:7], 'little'), int.from_bytes(digest[7:14], 'little')], dtype=torch.int64)
+    return digest[:8].hex(), ranks_that_differ(mine, group)
+
+
+def check_same_digest(signature, what, group=None):
+    """``check_same_plan`` for any string the ranks must agree on: its hash is all-gathered and a mismatch raises
+    ``RuntimeError`` on EVERY rank, naming the ranks that differ from rank 0.  Returns the hex digest."""
+    hexd, bad = _digest_and_who_differs(signature, group)
+    if bad:
+        raise RuntimeError('%s differs between ranks: rank(s) %s disagree with rank 0' % (what, bad))
+    return hexd
+
+
+_REDUCE_HOST = {'block': None, 'event': None}
+
+
+def all_reduce_flat(flat, group=None):
+    """``all_reduce(SUM)`` of the 1-D float32 tensor ``flat`` in place, on the current stream; returns ``flat``.  A no-op
+    without a process group.  Under ``nccl`` the collective is enqueued on the device and the host does not wait.  Under
+    ``gloo`` a device tensor goes through a pinned host block -- device to host, wait, reduce on the CPU, back to the
+    device -- so this path WAITS; it exists so that tests and boxes without RCCL run the same code.  A host tensor is
+    reduced where it is."""
+    if not group_active():
+        return flat
+    if not flat.is_cuda or not _host_backend(group):
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+        return flat
+    h = _REDUCE_HOST
+    if h['event'] is not None:
+        h['event'].synchronize()                             # (the block's last copy back to a device has left it)
+    if h['block'] is None or h['block'].numel() < flat.numel():
+        cap = max(h['block'].numel() if h['block'] is not None else 0, 1 << 16)
+        while cap < flat.numel():
+            cap *= 2
+        h['block'] = torch.empty(cap, dtype=torch.float32).pin_memory()
+    host = h['block'][:flat.numel()]
+    with torch.cuda.device(flat.device):
+        host.copy_(flat, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        flat.copy_(host, non_blocking=True)
+        h['event'] = torch.cuda.Event()
+        h['event'].record()
+    return flat
+
+
+def reduce_sums(t, group=None):
+    """SUM over the ranks of a small float64 tensor (the loss sums and the sample count of ``Trainer``): reduced on the
+    device under ``nccl`` (no wait; a new device tensor), on the host under ``gloo`` (waits; a host tensor).  Without a
+    process group ``t`` itself."""
+    if not group_active():
+        return t
+    out = t.detach().to(device='cpu' if _host_backend(group) else t.device, dtype=torch.float64, copy=True)
+    dist.all_reduce(out, op=dist.ReduceOp.SUM, group=group)
+    return out
+
+
+def broadcast_module(module, src=0, group=None, parameters=True, buffers=True):
+    """Give every rank rank ``src``'s parameters and buffers (the BatchNorm running statistics among them): one broadcast
+    per dtype of the flattened tensors, on the device under ``nccl``, through the host under ``gloo``.  A no-op without a
+    process group."""
+    if not group_active():
+        return module
+    from torch._utils import _flatten_dense_tensors, _unflatten_dense_tensors
+    tensors = ([p.data for p in module.parameters()] if parameters else []) + (list(module.buffers()) if buffers else [])
+    by_kind = {}
+    for t in tensors:
+        if t.numel():
+            by_kind.setdefault((t.dtype, t.device), []).append(t)
+    with torch.no_grad():
+        for (_, device), ts in by_kind.items():
+            flat = _flatten_dense_tensors(ts)
+            if _host_backend(group) and flat.is_cuda:
+                host = flat.cpu()
+                dist.broadcast(host, src, group=group)
+                flat = host.to(device)
+            else:
+                dist.broadcast(flat, src, group=group)
+            for t, f in zip(ts, _unflatten_dense_tensors(flat, ts)):
+                t.copy_(f)
+    return module
 
 
 def build_plans_consistently(build_fn):

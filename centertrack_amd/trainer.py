@@ -15,14 +15,23 @@ package (``dla_seg.DLASeg``, ``heads.HeadFinetuner``), the loss is ``losses.Gene
 norm, the closing line the number of skipped steps as well, and ``ret`` gains ``'grad_norm'`` and ``'skipped'``; they
 come in the same device read as the loss sums, so the loop waits no more often.  With the guard off nothing changes.
 
-Not covered: more than one GPU (``DataParallel``), ``opt.debug > 0`` (the reference's drawing), the progress bar (a plain
-line is printed instead).
+More than one GPU: one process per GPU under torchrun, each with a full replica.  With a process
+group active (``parallel.init_from_env``), ``set_device`` broadcasts rank 0's module and calls ``optimizer.distribute()``,
+after which every ``step()`` averages the gradients over the ranks with one all-reduce; ``set_device(gpus, ..)`` accepts
+``len(gpus) > 1`` when it equals the group's world size, ``device`` being this rank's.  The loss sums and the sample count
+are added over the ranks at the reads above (no additional read), so ``ret`` is the global average and equal on every
+rank; rank 0 prints; after a train epoch the buffers (the BatchNorm running statistics) are broadcast from rank 0, so its
+checkpoint holds what ``DataParallel`` keeps.  BatchNorm itself stays per replica, and the caller shards the data
+(``DistributedSampler``, ``batch_size / world`` samples per rank).
+
+Not covered: single-process ``DataParallel`` (``chunk_sizes`` is ignored), synchronised BatchNorm, ``opt.debug > 0`` (the
+reference's drawing), the progress bar (a plain line is printed instead).
 """
 import time
 
 import torch
 
-from . import dcn_v2
+from . import dcn_v2, parallel
 from ._lib import CTError
 from .losses import GenericLoss
 from .optim import guard_options
@@ -72,9 +81,18 @@ class Trainer(object):
                           'detections there)' % (opt.debug,))
 
     def set_device(self, gpus, chunk_sizes, device):
-        if len(gpus) > 1:
-            raise CTError('centertrack_amd.trainer.Trainer runs on one GPU (gpus = %s): DataParallel is not covered'
-                          % (list(gpus),))
+        world = parallel.world_size()
+        if len(gpus) > 1 and not parallel.group_active():
+            raise CTError('centertrack_amd.trainer.Trainer runs on one GPU per process (gpus = %s): single-process '
+                          'DataParallel is not covered; start one process per GPU with torchrun and call '
+                          'parallel.init_from_env() first' % (list(gpus),))
+        if len(gpus) > 1 and len(gpus) != world:
+            raise CTError('centertrack_amd.trainer.Trainer: gpus = %s inside a process group of %d ranks (one rank per GPU)'
+                          % (list(gpus), world))
+        if world > 1 and self.optimizer is not None and not hasattr(self.optimizer, 'distribute'):
+            raise CTError('centertrack_amd.trainer.Trainer: training on %d ranks needs an optimizer of '
+                          'centertrack_amd.optim (got %s, which does not exchange gradients)'
+                          % (world, type(self.optimizer).__name__))
         self.device = device
         self.model_with_loss = self.model_with_loss.to(device)
         if self.optimizer is not None:
@@ -82,6 +100,10 @@ class Trainer(object):
                 for k, v in state.items():
                     if isinstance(v, torch.Tensor):
                         state[k] = v.to(device=device, non_blocking=True)
+        if parallel.group_active():                          # one replica per rank: start from rank 0's, exchange gradients
+            parallel.broadcast_module(self.model_with_loss, src=0)
+            if hasattr(self.optimizer, 'distribute'):
+                self.optimizer.distribute()
 
     def _get_losses(self, opt):
         loss_states = ['tot'] + [k for k in LOSS_ORDER if k in opt.heads]
@@ -111,8 +133,11 @@ class Trainer(object):
         counters = getattr(self.optimizer, 'guard_counters', None) if train else None
         guarded = counters is not None and getattr(self.optimizer, '_guard', None) is not None
         base = counters() if guarded else None
+        # one process per GPU: the sums and the count are added over the ranks at every read, and rank 0 prints
+        spread = parallel.group_active()
+        chatty = not spread or torch.distributed.get_rank() == 0
 
-        def line(host_sums, guard=None, closing=False):
+        def line(host_sums, count, guard=None, closing=False):
             text = '{}| {}: [{}][{}/{}]|Tot: {:.1f}s '.format(title, phase, epoch, done, num_iters, time.time() - start)
             for l, s in zip(names, host_sums):
                 text += '|{} {:.4f} '.format(l, s / count if count else 0.0)
@@ -122,15 +147,34 @@ class Trainer(object):
                     text += '|skipped {} '.format(guard[1])
             return text
 
+        def over_ranks():
+            """the loss sums with the sample count behind them, added over the ranks (a device tensor under nccl)"""
+            mine = sums if sums is not None else torch.zeros(len(names), dtype=torch.float64, device=device)
+            return parallel.reduce_sums(torch.cat([mine, torch.tensor([count], dtype=torch.float64, device=mine.device)]))
+
+        def read():
+            """the loss sums of this epoch in ONE device read: (sums, count) -- over all ranks when there are several"""
+            if spread:
+                host = over_ranks().cpu().tolist()
+                return host[:-1], int(host[-1])
+            return (sums.cpu().tolist() if sums is not None else [0.0] * len(names)), count
+
         def read_guarded():
-            """the loss sums and the guard's counters of this epoch in ONE device read: (sums, (mean norm, skipped))"""
+            """the loss sums and the guard's counters of this epoch in ONE device read: (sums, count, (mean norm, skipped));
+            the counters come from the averaged gradient and are the same on every rank"""
             cur = counters()
             if cur is None or sums is None:
-                return (sums.cpu().tolist() if sums is not None else [0.0] * len(names)), (0.0, 0)
-            host = torch.cat([sums, cur if base is None else cur - base]).cpu().tolist()
-            norm_sum, steps, skipped, _, nonfinite_steps = host[len(names):]
+                return read() + ((0.0, 0),)
+            cur = cur if base is None else cur - base
+            if spread:
+                host = torch.cat([over_ranks().to(cur.device), cur]).cpu().tolist()
+                host_sums, n = host[:len(names)], int(host[len(names)])
+            else:
+                host = torch.cat([sums, cur]).cpu().tolist()
+                host_sums, n = host[:len(names)], count
+            norm_sum, steps, skipped, _, nonfinite_steps = host[-5:]
             finite = steps - nonfinite_steps
-            return host[:len(names)], (norm_sum / finite if finite else 0.0, int(skipped))
+            return host_sums, n, (norm_sum / finite if finite else 0.0, int(skipped))
 
         with dcn_v2.trainable(train or dcn_v2.is_trainable()):
             for iter_id, batch in enumerate(data_loader):
@@ -152,21 +196,23 @@ class Trainer(object):
                 count += n
                 done = iter_id + 1
                 if print_iter > 0 and iter_id % print_iter == 0:
-                    if guarded:
-                        print(line(*read_guarded()))
-                    else:
-                        print(line(sums.cpu().tolist()))                  # the only per-iteration read, on request
+                    text = line(*(read_guarded() if guarded else read()))  # the only per-iteration read, on request
+                    if chatty:
+                        print(text)
                 del output, loss, loss_stats
         guard = None
         if guarded:
-            host_sums, guard = read_guarded()
+            host_sums, total, guard = read_guarded()
         else:
-            host_sums = sums.cpu().tolist() if sums is not None else [0.0] * len(names)   # waits for the epoch's last launch
-        ret = {l: (s / count if count else 0) for l, s in zip(names, host_sums)}
+            host_sums, total = read()                                     # waits for the epoch's last launch
+        ret = {l: (s / total if total else 0) for l, s in zip(names, host_sums)}
         if guarded:
             ret['grad_norm'], ret['skipped'] = guard
         ret['time'] = (time.time() - start) / 60.
-        print(line(host_sums, guard, closing=True))
+        if chatty:
+            print(line(host_sums, total, guard, closing=True))
+        if train and spread:            # rank 0's checkpoint holds what DataParallel keeps: replica 0's running statistics
+            parallel.broadcast_module(model_with_loss, src=0, parameters=False)
         return ret, results
 
     def val(self, epoch, data_loader):

@@ -1061,9 +1061,26 @@ typedef struct ct_optim_rec {
     long long numel;                /* > 0 */
     float s[CT_OPTIM_SCALARS];
     int first;                      /* SGD: this step creates the momentum buffer */
-    int reserved[13];
+    int reserved[11];
+    const float *src;               /* ct_optim_pack_grads only: where g is gathered from (the last 8 bytes; else NULL) */
 } ct_optim_rec;
 int ct_optim_step(const void *table, int n, long long chunks, int kind, void *stream);
+
+/* ---- gradient gather for data-parallel training (an addition under ABI 103) ----------------
+ * One launch that gathers the gradient of every tensor of the table into ONE flat buffer, so that the exchange between
+ * replicas is one collective.  Tensor t lives in the flat buffer at element offset prefix[t] * CT_OPTIM_CHUNK -- the
+ * chunk prefix the table already carries, so every tensor starts 16-byte aligned when the buffer does -- and the
+ * record's g points there; src is the tensor the gradient is read from (p.grad).  For chunk c of tensor t:
+ *   g[i] = src[i] * scale   (i < numel; one float32 product, no contraction)
+ *   g[i] = +0.0             (numel <= i < chunks_t * CT_OPTIM_CHUNK: the tail of the tensor's last chunk)
+ * so g must have room for whole chunks, and the packed buffer is a function of the gradients alone.  The walk is
+ * ct_optim_step's (grid min(chunks, 2048), strided, binary search in the prefix); 16-byte loads when src is 16-byte
+ * aligned, 16-byte stores when g is, element by element otherwise.  src is never written; a record whose src is NULL
+ * is left alone.  No atomics, no LDS, no workspace.  ct_optim_step, ct_optim_step_guarded and ct_optim_norms never
+ * read src: run on the same table afterwards, they read the gathered (and reduced) gradient through g.
+ * CT_ERR_ARG before anything is enqueued: a null table, n outside [1, CT_OPTIM_MAX_TENSORS], chunks outside
+ * [n, 2^31), a scale that is NaN or +-Inf. */
+int ct_optim_pack_grads(const void *table, int n, long long chunks, float scale, void *stream);
 
 /* ---- guarded optimizer step (an addition under ABI 103) -----------------------------------
  * The global gradient norm, torch.nn.utils.clip_grad_norm_'s clip coefficient and a "skip the step when a gradient is
