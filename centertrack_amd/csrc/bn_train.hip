@@ -91,7 +91,7 @@ __device__ __forceinline__ float act_grad(float z, float mean, float ka, float b
     if (!RELU) return gy;
     float t = bn_pre(z, mean, ka, beta);
     if (RES) t += r;
-    return t > 0.0f ? gy : 0.0f;
+    return !(t <= 0.0f) ? gy : 0.0f;           // (a NaN pre-activation passes gy: torch's threshold_backward)
 }
 
 template <bool RELU, bool RES>
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void bn_act_apply_kernel(BnArgs a)
         for (int i = 0; i < 4; ++i) {
             float t = bn_pre(z[i], mean[i], ga[i] * istd[i], be[i]);
             if (RES) t += rv[i];
-            y[i] = RELU ? fmaxf(t, 0.0f) : t;
+            y[i] = RELU ? ct_relu(t) : t;
         }
         st4(a.y + p * a.ldy + c, y);
     }

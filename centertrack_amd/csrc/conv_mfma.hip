@@ -74,7 +74,7 @@ __device__ __forceinline__ void pool_from_patch(const float *buf, int c0, float 
             if (j == 0) m = v;
             else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
+                for (int e = 0; e < 4; ++e) m[e] = ct_max_prop(m[e], v[e]);
             }
         }
         *reinterpret_cast<f32x4 *>(pool_y + (((size_t)n * Ho + oy) * Wo + ox) * pool_ld + c0 + kk * 16 + q * 4) = m;
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a)
 #pragma unroll
                         for (int mt = 0; mt < WM; ++mt)
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) pmax[mt][e] = fmaxf(pmax[mt][e], af[mt][e]);
+                            for (int e = 0; e < 4; ++e) pmax[mt][e] = ct_max_prop(pmax[mt][e], af[mt][e]);
                     }
                     if (tap == 8 && proj) {
 #pragma unroll

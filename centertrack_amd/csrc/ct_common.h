@@ -157,11 +157,26 @@ struct EpiArgs {
 
 __device__ __forceinline__ float ct_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
+// Non-finite values are carried as torch carries them: fmaxf / fminf return the OTHER operand when one is
+// NaN, so a ReLU, a pooling maximum or a clamp written with them turns a NaN into a finite number.  Every activation, pooling
+// maximum and clamp of the training path goes through these three instead.
+// IEEE 754-2019 maximum: NaN if either operand is NaN.  gfx950 has it as ONE instruction (v_maximum3_f32), the price of the
+// v_max_f32 behind fmaxf; written as a compare and a select it is two, and the second one showed in the benchmark (every
+// launch ends in an epilogue that is a serial chain at one stream).
+__device__ __forceinline__ float ct_maximum(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// torch.relu, v < 0 ? 0 : v: NaN stays NaN, -Inf becomes 0
+__device__ __forceinline__ float ct_relu(float v) { return ct_maximum(v, 0.0f); }
+// the running maximum of torch.max_pool2d, (b > a || b != b) ? b : a: a later value wins only if it is greater or NaN, and a
+// NaN once taken stays
+__device__ __forceinline__ float ct_max_prop(float a, float b) { return ct_maximum(a, b); }
+// torch.clamp(v, lo, hi): NaN fails both comparisons and stays
+__device__ __forceinline__ float ct_clamp_prop(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // scale / shift / residual / ReLU only (kernels whose host entry rejects the sigmoid and depth transforms)
 __device__ __forceinline__ float ct_epilogue_plain(const EpiArgs &e, float v, float sc, float sh, float r)
 {
     v = v * sc + sh + r;
-    return (e.flags & CT_RELU) ? fmaxf(v, 0.0f) : v;
+    return (e.flags & CT_RELU) ? ct_relu(v) : v;
 }
 
 // Apply scale/shift/residual/activation to one accumulator value of channel `co`.
@@ -169,7 +184,7 @@ __device__ __forceinline__ float ct_epilogue_value(const EpiArgs &e, float v, in
                                                    float r)
 {
     v = v * sc + sh + r;
-    if (e.flags & CT_RELU) v = fmaxf(v, 0.0f);
+    if (e.flags & CT_RELU) v = ct_relu(v);
     if (co >= e.sig_lo && co < e.sig_hi) v = 1.0f / (1.0f + expf(-v));
     if (co >= e.dep_lo && co < e.dep_hi) v = (1.0f / (1.0f / (1.0f + expf(-v)) + 1e-6f) - 1.0f) * e.depth_scale;
     return v;

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void maxpool2x2_kernel(const float *x, int N, 
         const f32x4 d = *reinterpret_cast<const f32x4 *>(src + (size_t)W * ldx + ldx);
         f32x4 m;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) m[i] = fmaxf(fmaxf(a[i], b[i]), fmaxf(c[i], d[i]));
+        for (int i = 0; i < 4; ++i) m[i] = ct_max_prop(ct_max_prop(ct_max_prop(a[i], b[i]), c[i]), d[i]);
         *reinterpret_cast<f32x4 *>(y + (((size_t)n * Ho + oy) * Wo + ox) * ldy + c4 * 4) = m;
     }
 }

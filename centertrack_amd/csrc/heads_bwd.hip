@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void heads_tail_gmid_kernel(TailArgs a)
         const int gp = p0 + p;
         if (gp < a.total) {
             const float m = a.mid[(size_t)gp * a.ldmid + ch];
-            a.gmid[(size_t)gp * a.ldgmid + ch] = m > 0.0f ? s[p] : 0.0f;      // torch's ReLU: gradient 0 at exactly 0
+            a.gmid[(size_t)gp * a.ldgmid + ch] = !(m <= 0.0f) ? s[p] : 0.0f;      // torch's ReLU: gradient 0 at exactly 0, passed where mid is NaN
         }
     }
 }

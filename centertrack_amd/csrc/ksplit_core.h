@@ -208,7 +208,7 @@ __device__ __forceinline__ void ksplit_conv_tile(const float *xin, int H, int W,
 #pragma unroll
                                 for (int mt = 0; mt < WM; ++mt)
 #pragma unroll
-                                    for (int e = 0; e < 4; ++e) pmax[mt][e] = fmaxf(pmax[mt][e], af[mt][e]);
+                                    for (int e = 0; e < 4; ++e) pmax[mt][e] = ct_max_prop(pmax[mt][e], af[mt][e]);
                             }
                             if (s == 8 && side) {
 #pragma unroll

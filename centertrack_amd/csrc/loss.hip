@@ -60,7 +60,7 @@ __device__ __forceinline__ float block_sum(float v, float *sh)
 __device__ __forceinline__ float focal_neg(float x, float gt)
 {
     const float s = sigmoidf_(x);
-    const float p = fminf(fmaxf(s, P_LO), P_HI);
+    const float p = ct_clamp_prop(s, P_LO, P_HI);
     float w = 1.f - gt;
     w *= w;
     w *= w;
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(LOSS_SLOT_THREADS) void loss_slot_reduce_kernel(Los
             np += mk;
             if (fwd) {
                 const float s = sigmoidf_(h.x[((size_t)(e / M) * C + (size_t)cat) * HW + (size_t)ind]);
-                const float p = fminf(fmaxf(s, P_LO), P_HI), q = 1.f - p;
+                const float p = ct_clamp_prop(s, P_LO, P_HI), q = 1.f - p;
                 pos += logf(p) * q * q * mk;
             }
         }
@@ -301,7 +301,7 @@ __device__ __forceinline__ float slot_grad(const LossHeadDev &h, int HW, int b, 
         if (!t) return 0.f;
         const float r = h.target[2 * bm + half];
         const float d = px[(size_t)c * HW] - (j == 2 ? sinf(r) : cosf(r));
-        return up * (fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f)) / den[1 + half];
+        return up * (fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : d))) / den[1 + half];      // (a NaN residual stays NaN, as in torch)
     }
     case CT_LOSS_BCE: {
         const int e = bm * h.C + c;

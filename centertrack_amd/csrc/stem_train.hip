@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void stem_sum_kernel(StemSumArgs a)
             const f32x4 ga = ld4(a.gamma[s] + c), be = ld4(a.beta[s] + c), mean = ld4(a.mean[s] + c), istd = ld4(a.invstd[s] + c);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float t = fmaxf(bn_pre(z[i], mean[i], ga[i] * istd[i], be[i]), 0.0f);
+                const float t = ct_relu(bn_pre(z[i], mean[i], ga[i] * istd[i], be[i]));
                 y[i] = s == 0 ? t : y[i] + t;
             }
         }

@@ -49,8 +49,9 @@ def weighted_bce(x, mask, ind, target):
 
 
 def _smooth_l1(d):
-    a = d.abs()
-    return torch.where(a < 1, 0.5 * d * d, a - 0.5)
+    # (torch's own op, as the reference calls it: a torch.where of the two branches would differentiate the branch not taken as
+    # well, 0 * Inf = NaN at an infinite d; tests/test_nonfinite_cpu.py)
+    return torch.nn.functional.smooth_l1_loss(d, torch.zeros_like(d), reduction='none')
 
 
 def bin_rot(x, mask, ind, rotbin, rotres):
@@ -61,7 +62,9 @@ def bin_rot(x, mask, ind, rotbin, rotres):
     loss = 0
     for k in (0, 1):
         z = pred[:, 4 * k:4 * k + 2] * m
-        loss = loss + (torch.logsumexp(z, 1) - z.gather(1, tb[:, k:k + 1]).squeeze(1)).mean()
+        # log_softmax, as the reference's cross_entropy: z - max - log(sum(exp(z - max))) meets Inf - Inf at an infinite logit
+        # and is NaN there, where torch.logsumexp would answer Inf
+        loss = loss - torch.log_softmax(z, 1).gather(1, tb[:, k:k + 1]).squeeze(1).mean()
         rows = tb[:, k] != 0
         if bool(rows.any()):
             loss = loss + _smooth_l1(pred[rows, 4 * k + 2] - torch.sin(tr[rows, k])).mean()
