@@ -167,6 +167,14 @@ class BnActDesc(ctypes.Structure):
                                   ('gres', ctypes.c_void_p), ('ldgres', ctypes.c_int)]
 
 
+class BnMergeDesc(ctypes.Structure):
+    _fields_ = [('rows', ctypes.c_void_p), ('world', ctypes.c_int), ('C', ctypes.c_int), ('ld', ctypes.c_int),
+                ('eps', ctypes.c_float),
+                ('mean', ctypes.c_void_p), ('var', ctypes.c_void_p), ('invstd', ctypes.c_void_p), ('unbiased', ctypes.c_void_p),
+                ('inv_count', ctypes.c_void_p), ('count', ctypes.c_void_p),
+                ('gamma', ctypes.c_void_p), ('beta', ctypes.c_void_p), ('beta_shifted', ctypes.c_void_p)]
+
+
 class StemConvDesc(ctypes.Structure):
     _fields_ = [('N', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
                 ('inp', ctypes.c_void_p * 3), ('w', ctypes.c_void_p * 3),
@@ -390,7 +398,8 @@ EXPORTS = ['ct_last_error', 'ct_version', 'ct_set_tuning', 'ct_packed_weight_ele
            'ct_frame_loop_forget_upload', 'ct_frame_loop_prestage', 'ct_stem_forward_parts', 'ct_signal_host',
            'ct_build_targets', 'ct_build_targets_header_words', 'ct_build_pose_targets', 'ct_build_inputs', 'ct_build_inputs_partials',
            'ct_optim_step', 'ct_slot_gather', 'ct_slot_fold',
-           'ct_optim_norms_workspace_bytes', 'ct_optim_norms', 'ct_optim_step_guarded', 'ct_optim_pack_grads']
+           'ct_optim_norms_workspace_bytes', 'ct_optim_norms', 'ct_optim_step_guarded', 'ct_optim_pack_grads',
+           'ct_bn_stats_row', 'ct_bn_merge_stats', 'ct_bn_act_backward_apply', 'ct_bn_relu_backward_apply']
 
 _lib = None
 
@@ -474,6 +483,10 @@ def load():
     lib.ct_bn_act_backward.argtypes = [ctypes.POINTER(BnActDesc), p]
     lib.ct_bn_act_workspace_bytes.restype = sz
     lib.ct_bn_act_workspace_bytes.argtypes = [ctypes.POINTER(BnActDesc)]
+    lib.ct_bn_stats_row.argtypes = [ctypes.POINTER(BnDesc), p, p]
+    lib.ct_bn_merge_stats.argtypes = [ctypes.POINTER(BnMergeDesc), p]
+    lib.ct_bn_act_backward_apply.argtypes = [ctypes.POINTER(BnActDesc), p, p, p]
+    lib.ct_bn_relu_backward_apply.argtypes = [ctypes.POINTER(BnDesc), p, p, p]
     lib.ct_maxpool2x2_backward.argtypes = [p, i, i, i, i, i, p, i, p, i, p, i, p]
     lib.ct_stem_conv_forward.argtypes = [ctypes.POINTER(StemConvDesc), p]
     lib.ct_stem_conv_backward.argtypes = [ctypes.POINTER(StemConvDesc), p]

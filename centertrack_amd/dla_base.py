@@ -67,7 +67,7 @@ def _unit_forward(x, conv, bn, res, relu, pool):
     z = ops.conv2d(x, ops.pack_weight(conv.weight.detach()), conv.out_channels, ks, stride)
     pooled = ops.maxpool2x2(x) if pool else None
     mean, invstd, batch = bn_statistics(bn, z, 'backbone')
-    y = ops.bn_act_apply(z, mean, invstd, bn.weight.detach(), bn.bias.detach(), res=res, relu=relu)
+    y = ops.bn_act_apply(z, mean, invstd, bn.weight.detach(), _train.bn_beta(batch, bn.bias.detach()), res=res, relu=relu)
     return y, pooled, (z, mean, invstd, batch)
 
 
@@ -100,9 +100,16 @@ class _ConvBnActFunction(torch.autograd.Function):
             gy = gy.contiguous()
             need_z = need_x or need_w
             # without the ReLU the residual's gradient is the incoming tensor itself: no kernel, no copy
-            gz, gr, gg, gb = ops.bn_act_backward(ctx.z, View(gy), ctx.mean, ctx.invstd, gamma.detach(), beta.detach(), ctx.batch,
-                                                 res=None if res is None else View(res), relu=ctx.relu, need_z=need_z,
-                                                 need_res=need_res and ctx.relu, need_gamma=need_gamma, need_beta=need_beta)
+            if isinstance(ctx.batch, _train.SyncedBatch):  # statistics over all ranks: sums -> all-reduce -> apply
+                gz, gr, gg, gb = _train.synced_bn_backward([dict(
+                    z=ctx.z, gy=View(gy), mean=ctx.mean, invstd=ctx.invstd, gamma=gamma.detach(), beta=beta.detach(),
+                    sync=ctx.batch, res=None if res is None else View(res), relu=ctx.relu, need_z=need_z,
+                    need_res=need_res and ctx.relu, need_gamma=need_gamma, need_beta=need_beta)])[0]
+            else:
+                gz, gr, gg, gb = ops.bn_act_backward(ctx.z, View(gy), ctx.mean, ctx.invstd, gamma.detach(), beta.detach(),
+                                                     ctx.batch, res=None if res is None else View(res), relu=ctx.relu,
+                                                     need_z=need_z, need_res=need_res and ctx.relu, need_gamma=need_gamma,
+                                                     need_beta=need_beta)
             if need_res:
                 gres = gr.buf if ctx.relu else gy
             if ctx.stride == 2:
@@ -169,10 +176,12 @@ def _stems_forward(inputs, layers):
     live = [s for s in range(3) if inputs[s] is not None]
     zs = ops.stem_conv_forward(inputs, [None if layers[s] is None else layers[s][0].weight.detach() for s in range(3)])
     means, invstds, batches = [None] * 3, [None] * 3, [False] * 3
+    # (on the synchronised path the stems share one all-gather)
+    stats = _train.bn_statistics_many([layers[s][1] if s in live else None for s in range(3)], zs, 'backbone')
     for s in live:
-        means[s], invstds[s], batches[s] = bn_statistics(layers[s][1], zs[s], 'backbone')
+        means[s], invstds[s], batches[s] = stats[s]
     gammas = [layers[s][1].weight.detach() if s in live else None for s in range(3)]
-    betas = [layers[s][1].bias.detach() if s in live else None for s in range(3)]
+    betas = [_train.bn_beta(batches[s], layers[s][1].bias.detach()) if s in live else None for s in range(3)]
     if trace is not None:
         for s in live:
             _emit(ops.bn_relu_apply(zs[s], means[s], invstds[s], gammas[s], betas[s]).buf)
@@ -205,8 +214,16 @@ class _StemsFunction(torch.autograd.Function):
         gzs, gg, gb = [None] * 3, [None] * 3, [None] * 3
         need_in = [inputs[s] is not None and need[s] for s in range(3)]
         need_w = [inputs[s] is not None and need[3 + s] for s in range(3)]
+        synced = [s for s in range(3) if inputs[s] is not None and isinstance(ctx.batches[s], _train.SyncedBatch)]
+        if synced:                                     # statistics over all ranks: the stems share one all-reduce
+            got = _train.synced_bn_backward([dict(
+                z=ctx.zs[s], gy=gyv, mean=ctx.means[s], invstd=ctx.invstds[s], gamma=gammas[s].detach(), beta=betas[s].detach(),
+                sync=ctx.batches[s], neck=True, need_z=need_in[s] or need_w[s], need_gamma=need[6 + s], need_beta=need[9 + s])
+                for s in synced])
+            for s, (gz, _, g, b) in zip(synced, got):
+                gzs[s], gg[s], gb[s] = gz, g, b
         for s in range(3):
-            if inputs[s] is None:
+            if inputs[s] is None or s in synced:
                 continue
             gzs[s], gg[s], gb[s] = ops.bn_relu_backward(ctx.zs[s], gyv, ctx.means[s], ctx.invstds[s], gammas[s].detach(),
                                                         betas[s].detach(), ctx.batches[s], need_z=need_in[s] or need_w[s],

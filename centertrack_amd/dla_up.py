@@ -55,7 +55,7 @@ def _deform_forward(x, mod):
     om = View(om.buf, 0, 27)
     z = ops.dcn_v2(x, om, ops.pack_weight(dcn.weight.detach()), dcn.out_channels, shift=dcn.bias.detach())
     mean, invstd, batch = bn_statistics(bn, z, 'DeformConv')
-    y = ops.bn_relu_apply(z, mean, invstd, bn.weight.detach(), bn.bias.detach())
+    y = ops.bn_relu_apply(z, mean, invstd, bn.weight.detach(), _train.bn_beta(batch, bn.bias.detach()))
     return y, (om, z, mean, invstd, batch)
 
 
@@ -79,9 +79,14 @@ class _DeformConvFunction(torch.autograd.Function):
         need_om = need_off or need_x                   # the input reaches the output through the offsets as well
         need_z = need_om or need_w or need_b
         xv, om = View(x), ctx.om
-        gz, ggamma, gbeta = ops.bn_relu_backward(ctx.z, View(gy.contiguous()), ctx.mean, ctx.invstd, gamma.detach(),
-                                                 beta.detach(), ctx.batch, need_z=need_z, need_gamma=need_gamma,
-                                                 need_beta=need_beta)
+        if isinstance(ctx.batch, _train.SyncedBatch):  # statistics over all ranks: sums -> all-reduce -> apply
+            gz, _, ggamma, gbeta = _train.synced_bn_backward([dict(
+                z=ctx.z, gy=View(gy.contiguous()), mean=ctx.mean, invstd=ctx.invstd, gamma=gamma.detach(), beta=beta.detach(),
+                sync=ctx.batch, neck=True, need_z=need_z, need_gamma=need_gamma, need_beta=need_beta)])[0]
+        else:
+            gz, ggamma, gbeta = ops.bn_relu_backward(ctx.z, View(gy.contiguous()), ctx.mean, ctx.invstd, gamma.detach(),
+                                                     beta.detach(), ctx.batch, need_z=need_z, need_gamma=need_gamma,
+                                                     need_beta=need_beta)
         gx = gw = gb = gwoff = gboff = None
         if need_z:
             wT = ops.pack_weight_t(weight.detach()) if need_om else None

@@ -626,6 +626,109 @@ def bn_relu_backward(z, gy, mean, invstd, gamma, beta, batch_stats, need_z=True,
     return _bn_backward('ct_bn_relu_backward', 'ct_bn_workspace_bytes', d, z, gy, need_z, need_gamma, need_beta)
 
 
+# ---- synchronised BatchNorm: the statistics as a row to gather, the merge of the gathered rows, and the
+# backward in two halves with the all-reduce of the sums between them
+
+def bn_row_floats(C):
+    """floats of one rank's row ``[mean[C] | var[C] | resid[C] | pixel count]``: ``mean + resid`` is the mean before its
+    rounding to float, the count is a 64-bit integer, stored twice so that the row is a multiple of 16 bytes with every byte
+    defined"""
+    return 3 * C + 4
+
+
+def bn_stats_row(z, eps, row):
+    """``bn_stats`` written as the row a merge takes: ``row`` is a contiguous fp32 ``[bn_row_floats(C)]``, 16-byte aligned;
+    mean and biased variance (the bits of ``bn_stats``) go straight into it, the mean's rounding residual and the pixel count
+    N*H*W behind them -> invstd of the local statistics.  Four launches, as ``bn_stats``."""
+    lib = _lib.load()
+    _bn_vec(row, bn_row_floats(z.C), z)
+    invstd = torch.empty(z.C, dtype=torch.float32, device=z.buf.device)
+    d = _bn_desc(_lib.BnDesc, z, None, invstd)
+    d.eps = eps
+    _ws = _workspace(lib, 'ct_bn_workspace_bytes', d, z.buf.device)
+    _lib.check(lib.ct_bn_stats_row(ctypes.byref(d), row.data_ptr(), _lib.stream_ptr()), 'ct_bn_stats_row')
+    return invstd
+
+
+class MergedStats(object):
+    """what ``bn_merge_stats`` leaves on the device: ``mean``, biased ``var``, ``invstd``, ``unbiased`` variance ([C] each),
+    ``inv_count`` ([1] fp32, 1 / the pixels of all rows), ``count`` ([1] int64) and, when gamma and beta were given, ``beta``
+    ([C]): beta shifted by what the rounding of the merged mean to float dropped, times gamma * invstd -- the vector to hand the
+    apply and backward calls in the place of beta (None otherwise)"""
+    __slots__ = ('mean', 'var', 'invstd', 'unbiased', 'inv_count', 'count', 'beta')
+
+
+def bn_merge_stats(rows, C, eps=1e-5, gamma=None, beta=None):
+    """The statistics of the union of ``world`` shards from their rows: ``rows`` is a 2-D fp32 device tensor, one row per rank
+    in rank order, each ``[mean[C] | var[C] | resid[C] | count]`` as ``bn_stats_row`` writes it (a column slice of a wider gathered block
+    is fine: the row pitch is its stride).  Pooled moments in double, the rows added in row order, one rounding to float; one
+    launch, bitwise reproducible -> ``MergedStats``.  ``gamma`` and ``beta`` (both or neither): the affine pair of the BatchNorm,
+    for ``MergedStats.beta``."""
+    lib = _lib.load()
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_cuda or rows.shape[1] < bn_row_floats(C) or \
+            (rows.shape[1] > 1 and rows.stride(1) != 1):
+        raise _lib.CTError('bn_merge_stats: rows must be a 2-d fp32 device tensor of at least %d floats per row' % bn_row_floats(C))
+    world = rows.shape[0]
+    dev = rows.device
+    if (gamma is None) != (beta is None):
+        raise _lib.CTError('bn_merge_stats: gamma and beta go together')
+    out = torch.empty(5 * C + 4, dtype=torch.float32, device=dev)
+    m = MergedStats()
+    m.mean, m.var, m.invstd, m.unbiased, m.inv_count = out[:C], out[C:2 * C], out[2 * C:3 * C], out[3 * C:4 * C], out[5 * C:5 * C + 1]
+    m.beta = None if beta is None else out[4 * C:5 * C]
+    m.count = torch.empty(1, dtype=torch.int64, device=dev)
+    d = _lib.BnMergeDesc()
+    d.rows, d.world, d.C, d.ld, d.eps = rows.data_ptr(), world, C, rows.stride(0) if world > 1 else rows.shape[1], eps
+    d.mean, d.var, d.invstd, d.unbiased = (t.data_ptr() for t in (m.mean, m.var, m.invstd, m.unbiased))
+    d.inv_count, d.count = m.inv_count.data_ptr(), m.count.data_ptr()
+    if beta is not None:
+        for t in (gamma, beta):
+            if t.numel() != C or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise _lib.CTError('bn_merge_stats: gamma and beta must be contiguous fp32 [%d] on %s' % (C, dev))
+        d.gamma, d.beta, d.beta_shifted = gamma.data_ptr(), beta.data_ptr(), m.beta.data_ptr()
+    _lib.check(lib.ct_bn_merge_stats(ctypes.byref(d), _lib.stream_ptr()), 'ct_bn_merge_stats')
+    return m
+
+
+def _bn_backward_sums(entry, query_name, d, z, gy, out):
+    """the first half of a batch-statistics backward: the call with gz = gres = NULL -> ``[sum g | sum g * xhat]`` as one [2C]"""
+    lib = _lib.load()
+    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
+        raise _lib.CTError('%s: gy does not have the shape of z' % entry[3:])
+    sums = torch.empty(2 * z.C, dtype=torch.float32, device=z.buf.device) if out is None else _bn_vec(out, 2 * z.C, z)
+    d.gy, d.ldgy = gy.ptr, gy.ld
+    d.gbeta, d.ggamma = sums.data_ptr(), sums.data_ptr() + 4 * z.C
+    _ws = _workspace(lib, query_name, d, z.buf.device)
+    _lib.check(getattr(lib, entry)(ctypes.byref(d), _lib.stream_ptr()), entry)
+    return sums
+
+
+def _bn_backward_apply(entry, d, z, gy, sums, inv_count, need_z):
+    """the second half: ``sums`` ([2C]) and ``inv_count`` ([1]) are the caller's device tensors -> gz (a view, or None)"""
+    if (gy.N, gy.H, gy.W, gy.C) != (z.N, z.H, z.W, z.C):
+        raise _lib.CTError('%s: gy does not have the shape of z' % entry[3:])
+    _bn_vec(sums, 2 * z.C, z)
+    _bn_vec(inv_count, 1, z)
+    d.gy, d.ldgy = gy.ptr, gy.ld
+    gz = new_view(z.N, z.H, z.W, z.C, z.buf.device) if need_z else None
+    if gz is not None:
+        d.gz, d.ldgz = gz.ptr, gz.ld
+    _lib.check(getattr(_lib.load(), entry)(ctypes.byref(d), sums.data_ptr(), inv_count.data_ptr(), _lib.stream_ptr()), entry)
+    return gz
+
+
+def bn_relu_backward_sums(z, gy, mean, invstd, gamma, beta, out=None):
+    """``[sum g | sum g * xhat]`` of ``bn_relu_backward`` under batch statistics (this shard's; ``out``: a [2C] to fill)"""
+    d = _bn_desc(_lib.BnDesc, z, mean, invstd, gamma, beta, _lib.CT_BN_BATCH_STATS)
+    return _bn_backward_sums('ct_bn_relu_backward', 'ct_bn_workspace_bytes', d, z, gy, out)
+
+
+def bn_relu_backward_apply(z, gy, mean, invstd, gamma, beta, sums, inv_count):
+    """gz of ``bn_relu_backward`` under batch statistics from ``sums`` (over every shard) and ``inv_count`` (1 / their pixels)"""
+    d = _bn_desc(_lib.BnDesc, z, mean, invstd, gamma, beta, _lib.CT_BN_BATCH_STATS)
+    return _bn_backward_apply('ct_bn_relu_backward_apply', d, z, gy, sums, inv_count, True)
+
+
 def upsample_add_backward(x, w, f, gy, need_x=True, need_w=True):
     """Gradients of ``upsample_add(x, w, f, skip)`` for the output gradient ``gy`` (NHWC views; ``w``: the module weight
     [C,1,2f,2f] or an ``upsample_weight`` result; ``x`` may be None without ``need_w``) -> ``(gx view, gw [C,1,2f,2f], gskip)``,
@@ -735,6 +838,24 @@ def bn_act_backward(z, gy, mean, invstd, gamma, beta, batch_stats, res=None, rel
         d.gres, d.ldgres = gr.ptr, gr.ld
     gz, gg, gb = _bn_backward('ct_bn_act_backward', 'ct_bn_act_workspace_bytes', d, z, gy, need_z, need_gamma, need_beta)
     return gz, gr, gg, gb
+
+
+def bn_act_backward_sums(z, gy, mean, invstd, gamma, beta, res=None, relu=True, out=None):
+    """``[sum g | sum g * xhat]`` of ``bn_act_backward`` under batch statistics (this shard's; ``out``: a [2C] to fill)"""
+    d = _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, True)
+    return _bn_backward_sums('ct_bn_act_backward', 'ct_bn_act_workspace_bytes', d, z, gy, out)
+
+
+def bn_act_backward_apply(z, gy, mean, invstd, gamma, beta, sums, inv_count, res=None, relu=True, need_z=True, need_res=False):
+    """``(gz view, gres view)`` of ``bn_act_backward`` under batch statistics from ``sums`` (over every shard) and ``inv_count``
+    (1 / their pixels); None for what was not asked for"""
+    if not (need_z or need_res):
+        return None, None
+    d = _bn_act_desc(z, mean, invstd, gamma, beta, res, relu, True)
+    gr = new_view(z.N, z.H, z.W, z.C, z.buf.device) if need_res else None
+    if gr is not None:
+        d.gres, d.ldgres = gr.ptr, gr.ld
+    return _bn_backward_apply('ct_bn_act_backward_apply', d, z, gy, sums, inv_count, need_z), gr
 
 
 def maxpool2x2_backward(x, gy, add=None, out=None):

@@ -118,9 +118,12 @@ def all_reduce_flat(flat, group=None):
     without a process group.  Under ``nccl`` the collective is enqueued on the device and the host does not wait.  Under
     ``gloo`` a device tensor goes through a pinned host block -- device to host, wait, reduce on the CPU, back to the
     device -- so this path WAITS; it exists so that tests and boxes without RCCL run the same code.  A host tensor is
-    reduced where it is."""
+    reduced where it is.  Every call that reaches a collective adds itself and its payload bytes to ``COLLECTIVES`` (two
+    integer additions), which tools/sync_bn_bench.py and the world-1 RCCL test read."""
     if not group_active():
         return flat
+    COLLECTIVES['all_reduce_flat'] += 1
+    COLLECTIVES['all_reduce_bytes'] += 4 * flat.numel()
     if not flat.is_cuda or not _host_backend(group):
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
         return flat
@@ -141,6 +144,120 @@ def all_reduce_flat(flat, group=None):
         h['event'] = torch.cuda.Event()
         h['event'].record()
     return flat
+
+
+_GATHER_HOST = {'block': None, 'event': None}
+
+# what the collectives of synchronised BatchNorm moved since the last reset: calls and payload bytes of this rank
+# (tools/sync_bn_bench.py reads them; two integer additions per collective)
+COLLECTIVES = {'all_gather_rows': 0, 'all_gather_bytes': 0, 'all_reduce_flat': 0, 'all_reduce_bytes': 0}
+
+
+def reset_collective_counts():
+    for k in COLLECTIVES:
+        COLLECTIVES[k] = 0
+
+
+def all_gather_rows(row, group=None):
+    """All-gather of the 1-D float32 tensor ``row`` (the same length on every rank) -> ``[world, len(row)]``, the ranks in
+    rank order, on the current stream; bytes are moved as they are.  Without a process group ``row`` as ``[1, len(row)]``.
+    Under ``nccl`` the collective is enqueued on the device and the host does not wait.  Under ``gloo`` a device tensor goes
+    through a pinned host block -- device to host, wait, gather on the CPU, back to the device -- so this path WAITS, exactly
+    like ``all_reduce_flat``; it exists so that tests and boxes without RCCL run the same code."""
+    row = row.reshape(-1)
+    if not group_active():
+        return row.view(1, -1)
+    world, n = dist.get_world_size(group), row.numel()
+    COLLECTIVES['all_gather_rows'] += 1
+    COLLECTIVES['all_gather_bytes'] += 4 * n
+    if not row.is_cuda or not _host_backend(group):
+        out = torch.empty((world, n), dtype=row.dtype, device=row.device)
+        dist.all_gather_into_tensor(out, row.contiguous(), group=group)
+        return out
+    h = _GATHER_HOST
+    if h['event'] is not None:
+        h['event'].synchronize()                             # (the block's last copy back to a device has left it)
+    need = (world + 1) * n
+    if h['block'] is None or h['block'].numel() < need:
+        cap = max(h['block'].numel() if h['block'] is not None else 0, 1 << 12)
+        while cap < need:
+            cap *= 2
+        h['block'] = torch.empty(cap, dtype=torch.float32).pin_memory()
+    send, recv = h['block'][:n], h['block'][n:need]
+    out = torch.empty((world, n), dtype=torch.float32, device=row.device)
+    with torch.cuda.device(row.device):
+        send.copy_(row, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        dist.all_gather_into_tensor(recv, send, group=group)
+        out.view(-1).copy_(recv, non_blocking=True)
+        h['event'] = torch.cuda.Event()
+        h['event'].record()
+    return out
+
+
+SYNC_BN_MARK = '_ct_sync_bn'
+
+
+class SyncBatchNormMark(object):
+    """what ``sync_batchnorm`` leaves on a ``nn.BatchNorm2d``: the process group of its statistics and the measurement knob"""
+    __slots__ = ('group', 'force')
+
+    def __init__(self, group, force):
+        self.group, self.force = group, force
+
+
+def sync_batchnorm(module, group=None, force=False):
+    """Mark every ``nn.BatchNorm2d`` under ``module`` (itself included): in training mode, with a process group of more than
+    one rank active, its batch statistics are then taken over the batches of ALL ranks of ``group`` (``None``: the default
+    group), forward and backward, as ``torch.nn.SyncBatchNorm`` does.  The mark is an attribute: no
+    module is replaced, state-dict keys, buffer names and checkpoints stay what they are.  ``sync_batchnorm(module, False)``
+    clears it.  Without a group, at world 1 or in eval mode a marked BatchNorm runs today's path, bit for bit.  ``force``
+    takes the synchronised path in a group of ONE rank as well: a measurement knob (tools/sync_bn_bench.py), nothing in the
+    product sets it.  Returns ``module``."""
+    for m in module.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            if group is False:
+                m.__dict__.pop(SYNC_BN_MARK, None)
+            else:
+                m.__dict__[SYNC_BN_MARK] = SyncBatchNormMark(group, bool(force))
+    return module
+
+
+def sync_batchnorm_of(bn):
+    """the ``SyncBatchNormMark`` under which ``bn`` takes the synchronised path NOW -- marked, a group active, more than one
+    rank (or forced) -- else ``None``.  Training mode is the caller's to check."""
+    mark = bn.__dict__.get(SYNC_BN_MARK)
+    if mark is None or not group_active():
+        return None
+    return mark if mark.force or dist.get_world_size(mark.group) > 1 else None
+
+
+def check_buffers_in_sync(module, group=None):
+    """``optim.Adam.check_in_sync`` for the buffers of ``module`` (the BatchNorm running statistics and counters): every rank
+    forms a checksum of their bits, the checksums are all-gathered, and ``RuntimeError`` is raised on EVERY rank, naming the
+    ranks that differ from rank 0.  A read that WAITS; a no-op without a process group."""
+    if not group_active():
+        return
+    bufs = [b for b in module.buffers() if b.numel() > 0]
+    if not bufs:
+        return
+    with torch.no_grad():
+        sums = torch.stack([_bits_as_int64(b).sum() for b in bufs])
+        weights = torch.arange(1, len(bufs) + 1, dtype=torch.int64, device=sums.device)
+        mine = torch.stack([sums.sum(), (sums * weights).sum()])         # (int64 wraps: a checksum)
+    bad = ranks_that_differ(mine, group)
+    if bad:
+        raise RuntimeError('centertrack_amd.parallel.check_buffers_in_sync: the buffers of rank(s) %s differ from those of '
+                           'rank 0' % (bad,))
+
+
+def _bits_as_int64(t):
+    t = t.detach().contiguous()
+    if t.dtype == torch.float32:
+        return t.view(torch.int32).to(torch.int64)
+    if t.dtype == torch.float64:
+        return t.view(torch.int64)
+    return t.to(torch.int64)
 
 
 def reduce_sums(t, group=None):

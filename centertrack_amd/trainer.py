@@ -21,11 +21,17 @@ after which every ``step()`` averages the gradients over the ranks with one all-
 ``len(gpus) > 1`` when it equals the group's world size, ``device`` being this rank's.  The loss sums and the sample count
 are added over the ranks at the reads above (no additional read), so ``ret`` is the global average and equal on every
 rank; rank 0 prints; after a train epoch the buffers (the BatchNorm running statistics) are broadcast from rank 0, so its
-checkpoint holds what ``DataParallel`` keeps.  BatchNorm itself stays per replica, and the caller shards the data
+checkpoint holds what ``DataParallel`` keeps.  BatchNorm stays per replica by default, and the caller shards the data
 (``DistributedSampler``, ``batch_size / world`` samples per rank).
 
-Not covered: single-process ``DataParallel`` (``chunk_sizes`` is ignored), synchronised BatchNorm, ``opt.debug > 0`` (the
-reference's drawing), the progress bar (a plain line is printed instead).
+``opt.sync_bn`` (an optional attribute): with a process group active ``set_device`` marks the model
+with ``parallel.sync_batchnorm``, after which every training-mode BatchNorm takes its statistics over the batches of all
+ranks, forward and backward, as ``torch.nn.SyncBatchNorm`` does.  The running statistics are then the same bits on every
+rank, so the broadcast of rank 0's buffers after a train epoch is skipped; ``check_in_sync()`` compares parameters and
+buffers across the ranks on request.
+
+Not covered: single-process ``DataParallel`` (``chunk_sizes`` is ignored), gradient accumulation, overlapping the
+collectives with the backward, ``opt.debug > 0`` (the reference's drawing), the progress bar (a plain line is printed instead).
 """
 import time
 
@@ -104,6 +110,23 @@ class Trainer(object):
             parallel.broadcast_module(self.model_with_loss, src=0)
             if hasattr(self.optimizer, 'distribute'):
                 self.optimizer.distribute()
+            if getattr(self.opt, 'sync_bn', False):          # BatchNorm statistics over the batches of all ranks
+                parallel.sync_batchnorm(self.model_with_loss.model)
+
+    def sync_bn(self):
+        """is the model's BatchNorm synchronised: ``opt.sync_bn`` with a process group active"""
+        return bool(getattr(self.opt, 'sync_bn', False)) and parallel.group_active()
+
+    def check_in_sync(self):
+        """Compare the replicas on request: the parameters (``optimizer.check_in_sync``) and the buffers -- the BatchNorm
+        running statistics and counters -- of every rank against rank 0's; raises on EVERY rank, naming the ranks that
+        differ.  A read that WAITS.  The buffers agree after a train epoch (the broadcast) or, with ``opt.sync_bn``, always."""
+        if hasattr(self.optimizer, 'check_in_sync'):
+            self.optimizer.check_in_sync()
+        try:
+            parallel.check_buffers_in_sync(self.model_with_loss)
+        except RuntimeError as e:
+            raise CTError(str(e))
 
     def _get_losses(self, opt):
         loss_states = ['tot'] + [k for k in LOSS_ORDER if k in opt.heads]
@@ -211,7 +234,12 @@ class Trainer(object):
         ret['time'] = (time.time() - start) / 60.
         if chatty:
             print(line(host_sums, total, guard, closing=True))
-        if train and spread:            # rank 0's checkpoint holds what DataParallel keeps: replica 0's running statistics
+        if train and spread and not self.sync_bn():
+            # rank 0's checkpoint holds what DataParallel keeps: replica 0's running statistics.  (Under synchronised BatchNorm
+            # every rank moved its buffers with the same merged statistics: they are equal already.  That rests on EVERY
+            # BatchNorm of the model going through ``_train.bn_statistics`` under ``dcn_v2.trainable()`` on every rank, which
+            # the train phase above guarantees for this package's modules; a BatchNorm that runs on torch instead -- the stems
+            # of a first width other than 16 -- keeps per-rank statistics, and ``check_in_sync()`` is how to find out.)
             parallel.broadcast_module(model_with_loss, src=0, parameters=False)
         return ret, results
 

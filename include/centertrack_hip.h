@@ -490,6 +490,45 @@ typedef struct ct_bn_act_desc {
 int ct_bn_act_apply(const ct_bn_act_desc *d, void *stream);
 int ct_bn_act_backward(const ct_bn_act_desc *d, void *stream);
 size_t ct_bn_act_workspace_bytes(const ct_bn_act_desc *d);
+/* Synchronised BatchNorm (statistics over the batches of all ranks of a data-parallel job); additions under ABI 103.
+ * ct_bn_stats_row: ct_bn_stats of the map of `d` (d->mean and d->var are not read; invstd, eps and the workspace as there),
+ *   written as the row a merge takes, 3 C + 4 floats, 16-byte aligned:
+ *     [ mean[C] | var[C] (biased) | resid[C] | P, P ]
+ *   mean, var and invstd have the bits of ct_bn_stats; mean + resid is the mean before its rounding to float; P = N*H*W as a
+ *   64-bit integer, stored twice (the row is a multiple of 16 bytes with every byte defined: a gather moves bytes).
+ * ct_bn_merge_stats: `world` such rows on the device, row r at rows + r * ld floats, one per rank in rank order (ld >= 3 C + 2,
+ *   even; rows 8-byte aligned).  Per channel, in double, the rows added in row order, each result rounded to float once:
+ *     m_r = mean_r + resid_r;  v_r = var_r - resid_r^2  (the variance about the rounded mean, taken to the true one)
+ *     N = sum P_r;  mean = sum P_r m_r / N;  var = (sum P_r v_r + sum P_r (m_r - mean)^2) / N
+ *     invstd = 1 / sqrt(var + eps) from the rounded var, as ct_bn_stats forms it;
+ *     unbiased = var N / (N - 1);  *inv_count = 1 / N;  *count = N (count may be NULL)
+ *   The counts live on the device, so the host cannot check them: N >= 2 with every P_r >= 1 is the CALLER's contract (N = 1
+ *   leaves Inf or NaN in unbiased, N <= 0 in everything).  A non-finite mean_r or var_r makes that channel's results
+ *   non-finite, as ct_bn_stats on the whole batch would; only a negative rounding residue of var is clamped to 0.
+ *     beta_shifted = fma(-gamma * invstd, mean - float(mean), beta)  (with gamma, beta, beta_shifted given): the kernels behind
+ *       the merge form fma(z - mean, a, beta) with the FLOAT mean; handed beta_shifted in the place of beta, forward and
+ *       backward alike, they compute a (z - mean_in_double) + beta.  gbeta and ggamma are not affected.
+ *   world == 1 hands the row's mean and var back bit for bit (resid is not applied) and beta_shifted = beta.  The same rows give the same bits on
+ *   every rank and in every run.
+ * ct_bn_act_backward_apply / ct_bn_relu_backward_apply: the second half of ct_bn_act_backward / ct_bn_relu_backward under
+ *   CT_BN_BATCH_STATS.  The first half is that call with gz = gres = NULL: it leaves sum g in gbeta and sum g * xhat in ggamma.
+ *   sums = [ sum g [C] | sum g * xhat [C] ] (16-byte aligned) and *inv_count are device memory of the caller: with sums added
+ *   over the ranks and inv_count from ct_bn_merge_stats,
+ *     gz = a * (g - inv_count * sum g - xhat * inv_count * sum g * xhat);  gres = g
+ *   No workspace; ggamma, gbeta, var, eps are not read. */
+typedef struct ct_bn_merge_desc {
+    const float *rows; int world, C, ld;
+    float eps;
+    float *mean; float *var; float *invstd; float *unbiased;   /* [C] each */
+    float *inv_count;                                          /* [1] */
+    long long *count;                                          /* [1] or NULL */
+    const float *gamma; const float *beta;                     /* [C] each, with beta_shifted; or all three NULL */
+    float *beta_shifted;                                       /* [C]: beta - gamma * invstd * (mean - float(mean)) */
+} ct_bn_merge_desc;
+int ct_bn_stats_row(const ct_bn_desc *d, float *row, void *stream);
+int ct_bn_merge_stats(const ct_bn_merge_desc *d, void *stream);
+int ct_bn_act_backward_apply(const ct_bn_act_desc *d, const float *sums, const float *inv_count, void *stream);
+int ct_bn_relu_backward_apply(const ct_bn_desc *d, const float *sums, const float *inv_count, void *stream);
 /* ct_maxpool2x2_backward: the backward of ct_maxpool2x2 (H, W = the INPUT grid, even).  x: the pool's input [N,H,W,C]; gy:
  *   [N,H/2,W/2,C]; gx [N,H,W,C]: each window's gradient goes to its first maximum in row-major order (torch's rule: a window of
  *   equal values sends it to the top-left, -0.0 ties with 0, a NaN wins), the other three elements get 0; `add` (a view of the
