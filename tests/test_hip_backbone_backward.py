@@ -427,14 +427,20 @@ def compare(rep, name, hip, t64, t32, inputs):
 @pytest.mark.parametrize('training', [True, False], ids=['train', 'eval'])
 @pytest.mark.parametrize('name', list(BB.MODULES))
 def test_modules(device, name, training):
-    from centertrack_amd import dcn_v2, dla_base
+    from centertrack_amd import dla_base
     seed = BB.SEEDS[name]
+    sd = BB.random_params(seed, BB.MODULES[name][0](dla_base))
+    check_module(device, name, training, sd, seed, '%s %s' % (name, 'train' if training else 'eval'))
+
+
+def check_module(device, name, training, sd, seed, title):
+    """forward, every gradient, the moved running statistics and the bitwise repeat of the module ``name`` of
+    ``_backbone_bwd.MODULES`` under the state dict ``sd`` (tests/test_hip_ckpt_weights.py brings its own) -> the Report's rows"""
+    from centertrack_amd import dcn_v2, dla_base
     mod = BB.MODULES[name][0](dla_base)
-    sd = BB.random_params(seed, mod)
     mod.load_state_dict(sd)
     mod = mod.to(device).train(training)
     inputs = BB.module_inputs(name, seed + 1)
-    title = '%s %s' % (name, 'train' if training else 'eval')
     hip = hip_run(name, mod, inputs, device, seed + 20)
     maps, gys = hip[3], hip[4]
     free64, free32 = (BB.reference(name, sd, inputs, None, training, dt) for dt in (torch.float64, torch.float32))
@@ -478,6 +484,7 @@ def test_modules(device, name, training):
         for y, want in zip(ys, hip[0]):
             assert torch.equal(y, want) and y.grad_fn is None and not y.requires_grad
     rep.check()
+    return dict(rows=rep.rows, gpar=hip[2], t64=t64, buffers=mod.state_dict())
 
 
 def test_forward_nhwc_returns_the_same_maps(device):

@@ -54,6 +54,16 @@ def test_forward_matches_oracle(device, golden_dir, name, shape, off_std, head_c
     np.testing.assert_allclose(plan['feat'].to_nchw().cpu().numpy(), feat.numpy(), atol=1e-3, rtol=1e-3)
     for k in heads:
         np.testing.assert_allclose(got[k].cpu().numpy(), want[k].numpy(), atol=1e-3, rtol=1e-3, err_msg=k)
+    # the bar of tests/test_hip_ckpt_weights.py beside the one above: err against the float64 oracle, relative to the tensor's
+    # maximum, within 10 x what the float32 oracle does on the same data (never below 10 x 2^-23 sqrt(4608))
+    import _ckpt_weights as C
+    with torch.no_grad():
+        t64, _ = C.oracle_run(sd, (x, pre, hm), heads, torch.float64)
+    rows = [('feature', plan['feat'].to_nchw().cpu(), feat)] + [('head ' + k, got[k].cpu(), want[k]) for k in heads]
+    rows = [(k, C.err(w32, t64[k]), C.err(g, t64[k])) for k, g, w32 in rows]
+    print('\n'.join('%-28s e32 %.2e  err %.2e  err / bound %.3f' % (k, e32, e, e / C.bound(e32)) for k, e32, e in rows))
+    for k, e32, e in rows:
+        assert e <= C.bound(e32), (k, e32, e, C.bound(e32))
     if off_std == 0.01 and shape[1] == 64 and name in ('mot', 'nusc') and head_conv == 256:      # (recorded at 256)
         g = np.load(os.path.join(golden_dir, 'model_forward.npz'))
         for k in heads:

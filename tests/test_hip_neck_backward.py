@@ -472,23 +472,38 @@ def ida_Ks(c):
 
 
 def test_idaup(device):
+    c = NB.IDA
+    check_idaup(device, NB.ida_params(71, c['o'], c['channels'], c['up_f']), 'idaup', 0.1)
+
+
+def idaup_inputs():
+    c = NB.IDA
+    return [NB.randn(72 + i, c['N'], ch, h, w).float() for i, (ch, (h, w)) in enumerate(zip(c['channels'], c['sizes']))]
+
+
+def check_idaup(device, sd, title, min_distance):
+    """one training call of the IDAUp of ``_neck_bwd.IDA`` under the state dict ``sd`` (tests/test_hip_ckpt_weights.py brings
+    its own), no sample coordinate of the float64 run closer than ``min_distance`` to an integer -> the Report's rows"""
     from centertrack_amd import dla_up
     c = NB.IDA
-    sd = NB.ida_params(71, c['o'], c['channels'], c['up_f'])
     mod = dla_up.IDAUp(c['o'], c['channels'], c['up_f'])
     mod.load_state_dict(sd)
     mod = mod.to(device).train()
     masks = record_masks(mod)
-    inputs = [NB.randn(72 + i, c['N'], ch, h, w).float() for i, (ch, (h, w)) in enumerate(zip(c['channels'], c['sizes']))]
+    inputs = idaup_inputs()
     H0, W0 = c['sizes'][0]
     gys = [(NB.randn(76 + i, c['N'], c['o'], H0, W0) / (c['N'] * H0 * W0) ** 0.5).float() for i in range(2)]
     hip = hip_run(mod, inputs, ida_call, gys, device)
-    free64, _ = check_masks('idaup', masks, inputs, ida_fn, sd, True)
-    assert NB.min_integer_distance(free64['trace']) >= 0.1
+    free64, _ = check_masks(title, masks, inputs, ida_fn, sd, True)
+    assert NB.min_integer_distance(free64['trace']) >= min_distance
     t64, t32 = (reference(ida_fn, sd, inputs, gys, True, dt, masks) for dt in (torch.float64, torch.float32))
-    rep = Report('idaup')
+    rep = Report(title)
     compare(rep, hip, t64, t32, inputs, ida_Ks(c), True)
+    for k in sd:                                                     # one training call: the running statistics moved as torch's
+        if k.endswith(('running_mean', 'running_var')):
+            rep.add(k, mod.state_dict()[k], t64['sd'][k], t32['sd'][k], ida_Ks(c)['par'](k))
     rep.check()
+    return dict(rows=rep.rows, gpar=hip[2], t64=t64, trace=free64['trace'])
 
 
 def test_idaup_three_sgd_steps(device):
